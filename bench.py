@@ -9,8 +9,10 @@ env runs -- what Robot(cfg.robot_cfg) generates: body-body collisions on, Chest 
 (uhc/smpllib/smpl_parser.py:327-328, smpl_robot.py:1087-1110, 1177-1198).  `--floor-only` runs the shipped static asset as it is
 (floor contacts only: rounds 1-3's headline; kept as the `floor_only` sub-line).
 value = env-steps/s summed over all ranks (weak scaling: envs shard across ranks, no data-path collective).
-After the timed region one full PPO update (GAE + 10 full-batch epochs, gradients all-reduced over RCCL when
-n_gpus > 1) over the collected samples is timed and reported as ppo_samples_per_s.
+A plain run sets up, warms up, times the steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.
+With --full, after the timed region: one full PPO update (GAE + 10 full-batch epochs, gradients all-reduced over RCCL
+when n_gpus > 1) over the collected samples, the PGS kernel timings, the probes of the other BASELINE configs and the
+CPU baselines.
 """
 import argparse
 import json
@@ -31,6 +33,7 @@ if ROOT not in sys.path:
 # read qpos, qvel, warm start, action, expert target; write qpos, qvel, qacc, body pos / quat / com
 ALGO_BYTES_PER_ENV_STEP = 8 * (76 + 75 + 75 + 105 + 69 + 76 + 75 + 75 + 75 + 100 + 75)
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write
 
 
 FAST_KERNEL = {False: "void uhc_step_kernel<0, 1, false>", True: "void uhc_step_kernel<0, 1, true>"}  # floor-only | with body-body contacts compiled in
@@ -162,7 +165,30 @@ def parse():
     p.add_argument("--no-ppo", action="store_true")
     p.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU plumbing checks)")
     p.add_argument("--same-device", action="store_true", help="plumbing check: every rank uses GPU 0")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true", help="after the headline also the PPO update, the PGS kernel timings, the probes of the other configs and "
+                   "the CPU baselines (each still subject to its --no-* switch); a plain run measures the headline only")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy (float64; "
+                   f"a fixed, seeded sample of the envs if the whole would exceed {DUMP_LIMIT >> 20} MB)")
+    a = p.parse_args()
+    if not a.full:
+        a.no_ppo = a.no_pgs_probe = a.no_probes = a.no_cpu_baseline = True
+    return a
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> (n_env, ...) host array of one control step.  Written as float64 .npy; when the whole exceeds DUMP_LIMIT, the same
+    rows of every array are kept -- a sorted sample of the envs drawn with default_rng(0), listed in env_ids.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row = sum(v.nbytes // max(len(v), 1) for v in arrays.values())
+    room = DUMP_LIMIT - 256 * (len(arrays) + 1)  # (.npy headers)
+    if row * n > room:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=max(1, room // (row + 8)), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["env_ids"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def cpu_baseline(agent, n_env_gpu):
@@ -558,6 +584,8 @@ def bench_ball_objects(args):
                               "failed_envs": int(sim.field(S.F_FAIL).sum().item())}}
     out["roofline"]["frac"] = out["roofline"]["achieved"] / HBM_PEAK_GBS
     out["workload_stats"]["large_tier_share_of_env_steps"] = float(big_tot.double().sum().item()) / (n_env * args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"qpos": sim.field(S.F_QPOS).cpu().numpy(), "qvel": sim.field(S.F_QVEL).cpu().numpy()})
     sim.close()
     return out
 
@@ -567,6 +595,8 @@ def main():
     if args.workload == "ball_objects":
         print(json.dumps(bench_ball_objects(args)))
         return
+    if args.only_probe and args.dump_outputs:
+        sys.exit("--dump-outputs writes the headline's outputs; --only-probe runs no headline")
     if args.only_probe:  # one probe alone (profiling runs: rocprofv3 around this process sees that workload's kernels only)
         torch.cuda.set_device(0)
         torch.set_default_dtype(torch.float64)
@@ -625,6 +655,13 @@ def main():
     iters = env.sim.field(S.F_SOLVER_ITER).cpu().numpy()
     overflow = int(env.sim.field(S.F_EFC_OVERFLOW).sum().item())
     batch, logger = agent.rollout_end()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the rollout receives for the last timed step: the batch's row of every env (observation the policy saw, sampled
+        # action, reward with end bonus / bootstrap, mask, exploration flag), the filtered observation the next step starts from, the physics state
+        last = lambda x: x.reshape(n_env, T, -1)[:, T - 1].cpu().numpy()
+        dump_outputs(args.dump_outputs, {"states": last(batch.states), "actions": last(batch.actions), "rewards": last(batch.rewards), "masks": last(batch.masks),
+                                         "exps": last(batch.exps), "next_states": agent._ro.state.cpu().numpy(),
+                                         "qpos": env.sim.field(S.F_QPOS).cpu().numpy(), "qvel": env.sim.field(S.F_QVEL).cpu().numpy()})
     per_rank = [n_env * args.steps / elapsed]
     if dist_on:
         tt = torch.tensor([elapsed], device="cuda" if args.backend == "nccl" else "cpu", dtype=torch.float64)

@@ -29,16 +29,29 @@ def test_reference_import_paths_resolve_to_this_build():
         import uhc.no_such_module  # noqa: F401
 
 
+def _load_bench(path, name):
+    """bench.py as a module, with this process's environment as it was: bench.py sets OMP_PROC_BIND / OMP_PLACES defaults at import, and a bench
+    subprocess started later by another test would inherit them and have its OpenMP runtime bind the main thread to one core at `import torch`."""
+    import importlib.util
+    import os
+    env = dict(os.environ)
+    try:
+        spec = importlib.util.spec_from_file_location(name, path)
+        bench = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(bench)
+    finally:
+        os.environ.clear()
+        os.environ.update(env)
+    return bench
+
+
 def test_bench_defaults_are_the_drivers_contract():
     """`python bench.py` with no flags: one GPU, a step count that finishes in minutes, the metric's configuration (1 024 envs, exact
     contact solve, float64 learner); the flags the driver passes exist."""
-    import importlib.util
     import os
     import sys
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("bench_cli", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
+    bench = _load_bench(os.path.join(ROOT, "bench.py"), "bench_cli")
     argv, sys.argv = sys.argv, ["bench.py"]
     try:
         a = bench.parse()
@@ -54,16 +67,49 @@ def test_bench_defaults_are_the_drivers_contract():
     assert (b.gpus, b.steps, b.warmup) == (8, 20, 5)
 
 
+def test_bench_plain_run_leaves_the_extras_to_full(tmp_path):
+    """A plain run measures the headline only; --full brings back the PPO update, the PGS timings, the probes and the CPU baselines (each still
+    behind its --no-* switch).  --dump-outputs keeps to its size cap with the same seeded rows of every array, listed in env_ids.npy."""
+    import os
+    import sys
+    import numpy as np
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bench = _load_bench(os.path.join(ROOT, "bench.py"), "bench_cli3")
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"]
+        a = bench.parse()
+        sys.argv = ["bench.py", "--full", "--no-ppo"]
+        b = bench.parse()
+    finally:
+        sys.argv = argv
+    assert not a.full and a.no_ppo and a.no_pgs_probe and a.no_probes and a.no_cpu_baseline and a.dump_outputs is None
+    assert b.full and b.no_ppo and not b.no_pgs_probe and not b.no_probes and not b.no_cpu_baseline
+    x = np.arange(4000.0).reshape(1000, 4)
+    y = np.ones((1000, 2), dtype=np.float32)
+    bench.DUMP_LIMIT = 20000
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), {"x": x, "y": y})
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["env_ids.npy", "x.npy", "y.npy"] and all(v.dtype == np.float64 for v in got.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in got) <= 20000
+    ids = got["env_ids.npy"].astype(int)
+    assert len(ids) > 100 and (np.diff(ids) > 0).all()
+    np.testing.assert_array_equal(got["x.npy"], x[ids])
+    for f in got:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f), got[f])
+    bench.DUMP_LIMIT = 64 << 20
+    bench.dump_outputs(str(tmp_path / "c"), {"x": x})
+    assert sorted(os.listdir(tmp_path / "c")) == ["x.npy"] and np.array_equal(np.load(tmp_path / "c" / "x.npy"), x)
+
+
 def test_bench_reads_every_committed_profile():
     """bench.py quotes two numbers from the committed profiles (contact-solve share of the stage profile, float64 VALU counters of the PMC
     pass); whatever a measurement pass leaves under profiles/ must parse -- a profile format change may not break the bench line."""
     import glob
-    import importlib.util
     import os
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("bench_cli2", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
+    bench = _load_bench(os.path.join(ROOT, "bench.py"), "bench_cli2")
     share, src = bench.contact_solve_share()
     assert src and 0.02 < share < 0.6
     c = bench.valu_f64_counters(bench.FAST_KERNEL[False])

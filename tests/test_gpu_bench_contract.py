@@ -1,4 +1,5 @@
-"""GPU: bench.py prints ONE JSON line with the keys the driver and the judge read (task contract), on a tiny workload."""
+"""GPU: bench.py prints ONE JSON line with the keys the driver and the judge read (task contract), on a tiny workload; --full adds the PPO
+update, the probes and the CPU baselines to it."""
 import json
 import os
 import subprocess
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--preroll", "3", "--envs", "64", "--clips", "8"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--preroll", "3", "--envs", "64", "--clips", "8", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -45,6 +46,35 @@ def test_bench_json_contract():
     assert d["workload_stats"]["nefc_mean"] >= d["floor_only"]["nefc_mean"] - 8  # (the headline's body-body rows add to the floor rows)
 
 
+def test_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline alone (no PPO update, PGS timings, probes or CPU baselines), and --dump-outputs writes the
+    last timed step's batch row, next observation and physics state of every env as float64 .npy; a second run with the same arguments
+    starts from the same inputs, so it writes the same arrays (to rounding)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--preroll", "3", "--envs", "64",
+                              "--clips", "8", "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["warmup"] == 2 and r["value"] == pytest.approx(64 * 3 / (r["ms_per_step"] * 3e-3), rel=1e-6)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in r, k
+        for k in ("ppo", "pgs", "cpu_baseline", "floor_only", "shapes", "ball_rollout", "configs4", "configs2_per_gpu"):
+            assert k not in r, k
+        got = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(got) == {"states", "actions", "rewards", "masks", "exps", "next_states", "qpos", "qvel"}
+        assert all(v.dtype == np.float64 and v.shape[0] == 64 and np.isfinite(v).all() for v in got.values())
+        assert got["actions"].shape == (64, 105) and got["qpos"].shape[1] == 76 and got["states"].shape == got["next_states"].shape
+        assert (got["masks"] == 0).all()  # rollout_end closes every episode at the pass's last step: the dump is that step's row
+        dumps.append(got)
+    for k in dumps[0]:
+        np.testing.assert_allclose(dumps[1][k], dumps[0][k], rtol=1e-6, atol=1e-6, err_msg=k)
+
+
 def test_headline_is_measured_at_steady_state():
     """with the default pre-roll (40 untimed steps, two episode lengths of the random-init policy) the timed region is past the transient
     of the common restart: its two halves agree (15 %: 25 steps of a stochastic episode turnover each; inside the transient the first half is 20-40 % off),
@@ -68,7 +98,7 @@ def test_bench_two_ranks_over_rccl():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (the round-end 8-GPU node); the one-GPU box runs the gloo variant below")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--preroll", "0", "--envs", "256", "--clips", "8", "--no-probes"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--preroll", "0", "--envs", "256", "--clips", "8", "--no-probes", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=1200,
                          env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert out.returncode == 0, out.stderr[-2000:]
@@ -87,7 +117,7 @@ def test_bench_spawns_its_own_ranks():
     """`python bench.py --gpus 2` without a launcher starts two ranks itself and reports the whole job.  On this one-GPU box both ranks
     share GPU 0, which RCCL refuses (duplicate device), so the plumbing check rides on gloo; on an N-GPU node the default backend is RCCL."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--backend", "gloo", "--steps", "4", "--warmup", "2", "--preroll", "0", "--envs", "64",
-                          "--clips", "8"], cwd=ROOT, capture_output=True, text=True, timeout=1200,
+                          "--clips", "8", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=1200,
                          env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

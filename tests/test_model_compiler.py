@@ -7,7 +7,7 @@ import pytest
 from tests.helpers import box_model, box_triangles, pendulum_model
 from uhc_amd.model import mjcf
 
-REF_XML = "/root/reference/assets/mujoco_models/humanoid_smpl_neutral_mesh.xml"
+REF_XML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "humanoid_smpl_neutral_mesh", "humanoid_smpl_neutral_mesh.xml")
 
 
 def test_box_mesh_mass_properties():
@@ -75,8 +75,9 @@ def test_asset_model_layout():
     assert m.geom_type[0] == mjcf.GEOM_PLANE and (m.geom_contype[1:] == 0).all() and (m.geom_conaffinity == 1).all()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_XML), reason="reference assets only exist in the build container")
 def test_asset_matches_fresh_compile_of_reference_xml():
+    """The committed asset against a fresh compile of the reference's humanoid MJCF (tests/golden/humanoid_smpl_neutral_mesh: the scene file and
+    the 24 STL meshes it names, as the reference ships them)."""
     from uhc_amd.sim import load_asset_model
     a = load_asset_model()
     b = mjcf.compile_mjcf_file(REF_XML)

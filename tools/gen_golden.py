@@ -581,6 +581,77 @@ def g10_config():
     save("g10_config", **out)
 
 
+def _enc(v):
+    """A Config attribute as JSON: arrays tagged (compared as float arrays), everything else as json writes it (inf included)."""
+    if isinstance(v, np.ndarray):
+        assert v.dtype.kind in "biuf", v.dtype
+        return {"__ndarray__": v.astype(np.float64).tolist()}
+    if isinstance(v, np.generic):
+        return v.item()
+    if isinstance(v, dict):
+        return {k: _enc(x) for k, x in v.items()}
+    if isinstance(v, list):
+        return [_enc(x) for x in v]
+    assert v is None or isinstance(v, (str, bool, int, float)), type(v)
+    return v
+
+
+def g15_config_all():
+    """Every yml under the reference's config/ with the attributes the reference's own Config gives it (85 of 115 load: the rest name model
+    files the reference does not ship, recorded as null).  Path attributes are left out: they name the generating machine's directories."""
+    import glob
+    import json
+    import tempfile
+    import yaml
+    from uhc.utils.config_utils.copycat_config import Config
+    ref_import.assert_is_reference(Config)
+    paths = ("cfg_dict", "base_dir", "cfg_dir", "model_dir", "result_dir", "log_dir", "tb_dir", "output", "output_dir", "data_dir", "mujoco_model_file",
+             "vis_model_file", "main_result_dir")
+    out = {}
+    for f in sorted(glob.glob(os.path.join(REF, "config", "**", "*.yml"), recursive=True)):
+        rel = os.path.relpath(f, os.path.join(REF, "config"))
+        cid = os.path.splitext(os.path.basename(f))[0]
+        cd = yaml.safe_load(open(f))
+        base = tempfile.mkdtemp()
+        os.symlink(os.path.join(REF, "assets"), os.path.join(base, "assets"))
+        try:
+            rc = Config(cfg_id=cid, base_dir=base, cfg_dict=json.loads(json.dumps(cd)))
+            attrs = {k: _enc(v) for k, v in vars(rc).items() if k not in paths}
+        except OSError:
+            attrs = None  # the config names a model file the reference does not ship
+        out[rel] = {"cfg_id": cid, "yml": cd, "attrs": attrs}
+    save("g15_config_all", configs=np.array(json.dumps(out)))
+
+
+def g16_boundary_helpers():
+    """get_qvel_fd_new, quat_mul_vec_batch, quaternion_from_euler_batch ('rzyx'), qpos_to_smpl, in_hull of the reference on seeded inputs."""
+    from scipy.spatial import ConvexHull
+    import uhc.utils.math_utils as rmu
+    import uhc.utils.transformation as rtf
+    from uhc.smpllib import smpl_mujoco as rsm
+    from uhc.smpllib.smpl_robot import in_hull as r_in_hull
+    from uhc_amd.sim import load_asset_model
+    from uhc_amd.smpllib.smpl_mujoco import smpl_to_qpose
+    ref_import.assert_is_reference(rmu.get_qvel_fd_new)
+    rng = np.random.default_rng(5)
+    q0, q1 = rng.normal(size=76), rng.normal(size=76)
+    for q in (q0, q1):
+        q[3:7] /= np.linalg.norm(q[3:7])
+    q1[7:12] += np.array([7.0, -7.0, 3.2, -3.2, 0.0])  # hinge differences beyond +-pi: the wrap
+    qs = rng.normal(size=(7, 4)); qs /= np.linalg.norm(qs, axis=1, keepdims=True)
+    vs = rng.normal(size=(7, 3))
+    ang = rng.uniform(-3, 3, size=(3, 9))
+    pts = rng.normal(size=(40, 3))
+    queries = rng.normal(scale=1.2, size=(200, 3))
+    model = load_asset_model()
+    qpos = smpl_to_qpose(rng.normal(scale=0.4, size=(5, 72)), model, trans=rng.normal(size=(5, 3)))
+    pose, trans = rsm.qpos_to_smpl(qpos.copy(), model)
+    save("g16_boundary_helpers", q0=q0, q1=q1, qvel=rmu.get_qvel_fd_new(q0.copy(), q1.copy(), 1 / 30),
+         qvel_heading=rmu.get_qvel_fd_new(q0.copy(), q1.copy(), 1 / 30, "heading"), qs=qs, vs=vs, rot=rtf.quat_mul_vec_batch(qs.copy(), vs.copy()),
+         ang=ang, eul=rtf.quaternion_from_euler_batch(ang[0].copy(), ang[1].copy(), ang[2].copy(), "rzyx"), pts=pts, queries=queries,
+         in_hull=np.asarray(r_in_hull(ConvexHull(pts), queries)), qpos=qpos, pose=pose, trans=trans)
+
+
 # --------------------------------------------------------------------------- G13 AMASS database processing
 def g13_process_amass():
     """process_qpos_list + the split rule of uhc/data_process/process_amass_db.py on a synthetic AMASS db; the SMPL height fix
@@ -702,6 +773,8 @@ def main():
     g10_config()
     g12_policy_mcp()
     g13_process_amass()
+    g15_config_all()
+    g16_boundary_helpers()
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 # summaries worth keeping are copied into profiles/ by hand.  Stages:
 #   tests     pytest -m gpu (the whole suite)
 #   loop      the ball-joint agent test (with its evaluation pass and fail-safe teleport) 20 x, each time as the first test of a fresh process
-#   bench     python bench.py (driver-style: defaults)
+#   bench     python bench.py --full (the headline with every probe, the PPO update and the CPU baselines)
 #   prof_headline   kernel trace + PMC passes of the headline workload (self-colliding model class), tag _selfcol
 #   prof_floor      kernel trace + VALU / FETCH / WRITE passes of --floor-only
 #   prof_configs4   kernel trace + VALU / FETCH / WRITE passes of the configs[4] rollout probe, and of ball_rollout
@@ -38,7 +38,7 @@ loop)
   done
   echo "ball-joint agent iteration + evaluation (fail-safe teleport), first test of a fresh process: $ok passed, $bad failed of 20" | tee -a ${O}_ball_agent_loop.txt ;;
 bench)
-  python bench.py > ${O}_bench.json 2> ${O}_bench.err
+  python bench.py --full > ${O}_bench.json 2> ${O}_bench.err
   cut -c1-600 ${O}_bench.json ;;
 prof_headline)
   B="python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-ppo --no-pgs-probe --no-probes"

@@ -7,7 +7,7 @@
 #   tests_fast  the GPU suite without the 200-step file (which `parity200` runs)
 #   soak        long synchronised rollouts of configs4 / ball_rollout / shapes (+ configs4 at 4096 envs): tier-4 env-steps, cap hits, dropped rows, step times
 #   probes4096  the two ball-joint probes at 4096 envs (efc_overflow must stay 0)
-#   ppo_prof    kernel trace of one PPO update (bench.py --no-probes --no-cpu-baseline --no-pgs-probe with a short rollout): which kernels the update spends its time in
+#   ppo_prof    kernel trace of one PPO update (bench.py --full --no-probes --no-cpu-baseline --no-pgs-probe with a short rollout): which kernels the update spends its time in
 # every other stage name is handed to tools/r04_pass.sh (tests, loop, bench, prof_headline, prof_floor, prof_configs4, prof_shapes, slowest, stage, meta).
 set -u
 TAG=${1:-r05_x}; shift
@@ -69,7 +69,7 @@ tests_fast)
   (timeout 1700 python -m pytest tests -m gpu -q --tb=short -rs --deselect tests/test_gpu_parity_200.py 2>&1 | grep -v amdgpu | tail -45) > ${O}_pytest_gpu.txt 2>&1
   tail -4 ${O}_pytest_gpu.txt ;;
 ppo_prof)
-  B="python $GRAFT_REPO_ROOT/bench.py --steps 8 --warmup 2 --preroll 6 --no-cpu-baseline --no-pgs-probe --no-probes"
+  B="python $PWD/bench.py --full --steps 8 --warmup 2 --preroll 6 --no-cpu-baseline --no-pgs-probe --no-probes"
   (cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_ppo -o kt -- $B > $GRAFT_REPO_ROOT/${O}_bench_ppo_under_rocprof.json 2> /tmp/ppo.err)
   python tools/rocpd_summary.py /tmp/prof_ppo/kt_results.db ${O}_ppo_kernel_stats.txt "$TAG: rocprofv3 --kernel-trace --stats -- bench.py --steps 8 --warmup 2 --preroll 6 --no-cpu-baseline --no-pgs-probe --no-probes (16 rollout steps of 1024 envs + two full PPO updates over 16384 samples: the update's kernels are the Cijk_* / elementwise rows)" > /dev/null
   head -30 ${O}_ppo_kernel_stats.txt | cut -c1-180 ;;
