@@ -2,9 +2,6 @@
 // the large tier's workgroups go on as tier 4 (Newton on the primal, uhc_primal.h) when an env does not fit or its working sets give up
 #define UHC_WITH_TIER4
 #include "uhc_physics_impl.h"
+#include "uhc_launch.h"
 
-extern "C" hipError_t uhc_launch_m1_big(const KernelArgs* A, const double* d_action, const double* d_tbase, const int* d_active, size_t lds_bytes, hipStream_t stream) {
-    hipLaunchKernelGGL((uhc_step_kernel<1, 3, true>), dim3(A->grid ? A->grid : A->n_env), dim3(UHC_WAVE), lds_bytes, stream, *A, d_action, d_tbase, d_active);
-    return hipGetLastError();
-}
-extern "C" hipError_t uhc_launch_m1_big_lds(size_t lds_bytes) { return hipFuncSetAttribute((const void*)uhc_step_kernel<1, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }
+UHC_ENV_LAUNCH(m1_big, 1, 3, true)

@@ -1,8 +1,5 @@
 // uhc_k_fast.hip -- one translation unit of the fused step kernel (instantiations split across files so that they compile in parallel).
 #include "uhc_physics_impl.h"
+#include "uhc_launch.h"
 
-extern "C" hipError_t uhc_launch_m0_fast(const KernelArgs* A, const double* d_action, const double* d_tbase, const int* d_active, size_t lds_bytes, hipStream_t stream) {
-    hipLaunchKernelGGL((uhc_step_kernel<0, 1, false>), dim3(A->grid ? A->grid : A->n_env), dim3(UHC_WAVE), lds_bytes, stream, *A, d_action, d_tbase, d_active);
-    return hipGetLastError();
-}
-extern "C" hipError_t uhc_launch_m0_fast_lds(size_t lds_bytes) { return hipFuncSetAttribute((const void*)uhc_step_kernel<0, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }
+UHC_ENV_LAUNCH(m0_fast, 0, 1, false)

@@ -1,8 +1,5 @@
 // uhc_k_fast_fwd_dense.hip -- one translation unit of the fused step kernel (instantiations split across files so that they compile in parallel).
 #include "uhc_physics_impl.h"
+#include "uhc_launch.h"
 
-extern "C" hipError_t uhc_launch_m1_fast_dense(const KernelArgs* A, const double* d_action, const double* d_tbase, const int* d_active, size_t lds_bytes, hipStream_t stream) {
-    hipLaunchKernelGGL((uhc_step_kernel<1, 1, true>), dim3(A->grid ? A->grid : A->n_env), dim3(UHC_WAVE), lds_bytes, stream, *A, d_action, d_tbase, d_active);
-    return hipGetLastError();
-}
-extern "C" hipError_t uhc_launch_m1_fast_dense_lds(size_t lds_bytes) { return hipFuncSetAttribute((const void*)uhc_step_kernel<1, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }
+UHC_ENV_LAUNCH(m1_fast_dense, 1, 1, true)

@@ -6,10 +6,6 @@
 #define UHC_WITH_TIER4
 #define UHC_NW4
 #include "uhc_physics_impl.h"
+#include "uhc_launch.h"
 
-extern "C" hipError_t uhc_launch_m0_huge_q(const KernelArgs* A, const double* d_action, const double* d_tbase, const int* d_active, size_t lds_bytes, hipStream_t stream) {
-    (void)d_active;
-    hipLaunchKernelGGL((uhc_step_queue_kernel<0, 4, true>), dim3(A->grid), dim3(UHC_QUEUE_THREADS), lds_bytes, stream, *A, d_action, d_tbase);
-    return hipGetLastError();
-}
-extern "C" hipError_t uhc_launch_m0_huge_q_lds(size_t lds_bytes) { return hipFuncSetAttribute((const void*)uhc_step_queue_kernel<0, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }
+UHC_QUEUE_LAUNCH(m0_huge_q, 4, UHC_QUEUE_THREADS)

@@ -1,0 +1,62 @@
+// uhc_plan.h -- what uhc_batch_create decides before it touches the device: knobs, topology tables, LDS layouts, schedules, launch sizes.
+// Pure host code (uhc_plan.cpp calls no hip* function); tests/test_batch_plan_cpu.py checks it without a GPU.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "uhc_host.h"
+
+// the UHC_* environment variables of batch creation, parsed and range-checked (read_knobs is the one place of the host code that reads the environment)
+struct BatchKnobs {
+    int dbg = 0;                    // UHC_DEBUG (KernelArgs::dbg; bits 8-12 only in -DUHC_EXPERIMENTS builds)
+    int marks[8] = {64, 16, -1, 56, 14, 10, 8, 7};  // UHC_TIER_MARKS "a,b,c,d,e,f,g,h" (marks[2] < 0: body-body marks follow the fast layout)
+    int fast_dense_got = 0, fast_dense_kib = 0, fast_dense_rows = 0, fast_dense_con = 0;  // UHC_FAST_DENSE "KiB,dense rows[,contacts]": fields read, their values
+    bool fast_dcol_own = false;     // UHC_FAST_DCOL_OWN=1
+    bool lds_pad_fast = false;      // UHC_LDS_PAD_FAST=KiB
+    int lds_pad_fast_kib = 0;
+    bool force_general = false;     // UHC_FORCE_GENERAL=1
+    int tiers = 0;                  // UHC_TIERS: 2, 3 or 0 (unset / anything else: four tiers)
+    int guard = 0;                  // UHC_GUARD_LDS: 1 guard words, 2 the self-test (one guard ON qpos of the fast tier), 0 off
+    int q2_div = 1, q2_wait_min = 16, q2_max = 256, q3_max = 32, q4_max = 16;  // UHC_Q2_DIV >= 1, UHC_Q2_WAIT >= 1, UHC_Q2_MAX >= 16, UHC_Q3_MAX >= 2, UHC_Q4_MAX >= 0
+    int t4_rows = 0;                // UHC_T4_ROWS >= 0
+};
+BatchKnobs read_knobs();
+
+struct BatchPlan {
+    KernelArgs A;  // every pointer-free field batch creation decides; the pointers are null (uhc_batch_create uploads the tables below)
+    size_t lds_bytes = 0, lds_bytes_fast = 0, lds_bytes_big = 0;
+    bool use_fast = true;
+    int n_trailing_free = 0;
+    std::vector<int> body_depth, body_rootid, body_nsub, body_lastdof, dof_depth, dof_ndesc, dof_rootid;
+    std::vector<short> dof_anc, m_row, m_col;
+    std::vector<unsigned short> m_ij;
+    std::vector<unsigned char> ncommon;
+    std::vector<int> pg1, pg2, cg1, cg2;  // statically filtered collision pairs: (plane, hull), (hull, hull)
+    std::vector<double> model_blob;       // the models' numeric blobs, one after the other (DevNumOff::stride each)
+    std::vector<unsigned int> fac_prog, sol_back, sol_fwd, chain;
+    std::vector<int> dof_act;
+    std::vector<int> vf_body;    // explicit RFC only
+    std::vector<int> guard_tab;  // UHC_GUARD_LDS: 4 x 64 ints (KernelArgs::guard_tab); empty otherwise
+};
+// -> 0, or 1 with *err set: every refusal of uhc_batch_create that does not need the device
+int plan_batch(const UhcModel* const* models, int n_models, const int32_t* env_model, int n_env, const UhcCtrlDesc* ctrl, const BatchKnobs& knobs,
+               BatchPlan* out, std::string* err);
+
+// sticky tiers: the sizes of one step's consumer launches from the newest queue counts the host has seen (launch() in uhc_capi.cpp)
+struct StickyInputs {
+    int est2, est3, est4;  // queue lengths of the general / large tier at the end of the newest step seen; env-steps that went through tier 4
+    int est2_then;         // the general tier's queue in the step est4 is from
+    int handed2;           // how many of est2 came in during the step
+    int n_env, n_cu;
+    size_t lds_bytes_fast;
+    bool large_first;      // the large tier's consumers are launched before the general tier's
+    int last_tier;
+    bool queues_off;       // no waiting consumers (back-off after a consumer gave up)
+    int q2_div, q2_wait_min, q2_max, q3_max, q4_max;
+    bool fixed_cap2;       // measurement switch (UHC_DEBUG bit 11 of -DUHC_EXPERIMENTS builds): a fixed cap UHC_Q2_MAX on the general tier's consumers
+};
+struct StickySizes {
+    bool queues, waiting, q3, q4, launch4;
+    int grid2, grid3, grid4, n_wait, sticky_mask;
+};
+StickySizes plan_sticky_step(const StickyInputs& in);
