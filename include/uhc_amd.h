@@ -143,11 +143,13 @@ enum UhcField {
                               * capacity were DROPPED in this step (UHC_F_EFC_OVERFLOW is the sticky version, cleared by the env's next set_state);
                               * without tier 4 a forward pass that dropped rows gets a bounded exact attempt and at most 32 sweeps (bits 1 and 7) */
     UHC_F_TIER = 17,         /* int32 [n_env] 1 | 2 | 3 | 4: the tier the env's next step starts in under uhc_batch_set_kernel_path(2) */
-    UHC_F_HANDON_WHY = 18    /* int32 [n_env] diagnostic of the last step: bits 0-7 why the fast tier handed the env on, bits 8-15 why the general tier did
+    UHC_F_HANDON_WHY = 18,   /* int32 [n_env] diagnostic of the last step: bits 0-7 why the fast tier handed the env on, bits 8-15 why the general tier did
                               * (1 contacts, 2 constraint rows, 4 body-body row slots, 8 packed row storage, 16 MPR candidate list beyond the tier's
                               * capacity, 32 the working sets did not finish: more force-carrying rows in an island than a working set holds), bits 16-23 the
                               * substep of the last hand-on, bits 24-31 why the LARGE tier handed the env on to tier 4 (the same reason bits);
                               * 0 = the env stayed in the tier it started in */
+    UHC_F_QACC_WARMSTART = 19, /* [n_env][nv] data.qacc_warmstart: what the next step's first solve starts from */
+    UHC_F_COST = 20          /* int32 [n_env] how close the env's last step came to any capacity of the fast tier, in sixty-fourths: orders the fast tier's launch */
 };
 
 const char* uhc_last_error(void);
@@ -230,6 +232,12 @@ int32_t uhc_batch_simulate(UhcBatch* b, const double* d_action, const double* d_
  * on the events) and returns the summed kernel time and the number of launches since the last call. */
 int32_t uhc_batch_set_timing(UhcBatch* b, int32_t enable);
 int32_t uhc_batch_kernel_time(UhcBatch* b, double* total_ms, int32_t* launches);
+/* Workgroups that gave up waiting since the batch was created (synchronises the batch's stream): queue consumers of the sticky tiers whose producers did
+ * not run beside them, and workgroups of the chunked fast tier (UHC_FAST_CHUNK) whose env's previous chunk did not finish within 50 ms.  Nothing is
+ * dropped when one does -- the chained launches / the workgroup that holds the env take over -- but a healthy run reports 0.
+ * n_slow (may be NULL): queue consumers that left after 50 ms behind producers that WERE running beside them (some had finished) but had not all finished:
+ * a sign of a very slow env-step in the tier below, not of launches that cannot overlap; the host does not act on it. */
+int32_t uhc_batch_give_ups(UhcBatch* b, int32_t* n, int32_t* n_slow);
 
 /* What the fast kernel does with an env that has more than 16 contacts or 64 constraint rows:
  * 0 (default) = leave it to the general kernel (exact, costs a second pass whenever one env overflows);

@@ -34,6 +34,13 @@ def analyze(prof, n, step, lines):
             continue
         q = lambda x: " ".join(f"{v:6.2f}" for v in np.nanpercentile(x, [0, 25, 50, 75, 90, 99, 100]))
         lines.append(f"tier {tier}: {m.sum():4d} envs | start  (min 25% 50% 75% 90% 99% max) {q(s[m])} | end {q(e[m])} | duration {q((e - s)[m])}")
+    # the fast tier in substep chunks (UHC_FAST_CHUNK): tier 1's start is the first chunk's, its end the last chunk's (or the hand-on); word 24 sums the ticks the
+    # env's later chunks spent waiting for the previous one (their workgroups hold a place meanwhile)
+    cw = prof[:, 24].cpu().numpy().astype(np.float64) * 1e-5
+    if (cw > 0).any():
+        m1 = ~np.isnan(ms[:, 0])
+        lines.append(f"tier 1 in chunks: {int((cw > 0).sum())} envs waited between chunks | place-ms spent waiting per env (min 25% 50% 75% 90% 99% max) "
+                     + " ".join(f"{v:6.2f}" for v in np.percentile(cw[m1], [0, 25, 50, 75, 90, 99, 100])) + f" | sum {cw[m1].sum():.0f} place-ms of {np.nansum((ms[:, 1] - ms[:, 0])[m1]):.0f} between first-chunk start and last-chunk end")
     h1 = ~np.isnan(ms[:, 2]) & ~np.isnan(ms[:, 0])   # handed on by tier 1 this step
     if h1.any():
         wait = ms[h1, 2] - ms[h1, 1]

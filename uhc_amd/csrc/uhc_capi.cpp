@@ -224,7 +224,8 @@ static int alloc_state(UhcBatch* b, const UhcModel* const* models, const int32_t
     TRY(dalloc(b, E * nq, &S.qpos)); TRY(dalloc(b, E * nv, &S.qvel)); TRY(dalloc(b, E * nv, &S.qacc)); TRY(dalloc(b, E * nv, &S.qacc_ws));
     TRY(dalloc(b, E * 3 * nb, &S.xpos)); TRY(dalloc(b, E * 4 * nb, &S.xquat)); TRY(dalloc(b, E * 3 * nb, &S.xipos));
     TRY(dalloc(b, 4, &S.path_stats));
-    TRY(dalloc(b, E * A.t.nM, &S.qM)); TRY(dalloc(b, 5 * E, &S.redo)); S.pend2 = S.redo + E; S.pend3 = S.redo + 2 * E; S.resume = S.redo + 3 * E; S.why = S.redo + 4 * E; TRY(dalloc(b, 1, &S.q_abort));
+    TRY(dalloc(b, E * A.t.nM, &S.qM)); TRY(dalloc(b, 6 * E + 1, &S.redo)); S.pend2 = S.redo + E; S.pend3 = S.redo + 2 * E; S.resume = S.redo + 3 * E; S.why = S.redo + 4 * E; TRY(dalloc(b, 2, &S.q_abort));
+    A.chunk_done = S.redo + 5 * E; A.ticket = S.redo + 6 * E; TRY(dalloc(b, E * UHC_CHUNK_REC, &A.chunk_rec));  // (the chunked fast tier: progress words and ticket counter are reset with redo .. why)
     TRY(dalloc(b, E, &S.tier)); TRY(dalloc(b, E, &b->tier_now)); S.tier_now = b->tier_now; TRY(dalloc(b, E, &S.cost));
     if (!(A.dbg & 8)) TRY(dalloc(b, E, &b->d_order));  // (UHC_DEBUG bit 3: the fast tier launches in env order)
     TRY(dalloc(b, 3 * E, &b->d_lists)); TRY(dalloc(b, 8, &b->d_counts)); TRY(dalloc(b, 8, &b->d_cursors)); TRY(dalloc(b, 8, &b->d_fin));
@@ -245,10 +246,10 @@ static int alloc_state(UhcBatch* b, const UhcModel* const* models, const int32_t
         HIP_OK(hipMemcpy(S.qpos, q0.data(), q0.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     const int64_t n = (int64_t)E;
-    const UhcBatch::Field fields[19] = {{S.qpos, n * nq}, {S.qvel, n * nv}, {S.xpos, n * 3 * nb}, {S.xquat, n * 4 * nb}, {S.xipos, n * 3 * nb}, {S.qM, n * A.t.nM}, {S.bias, n * nv},
+    const UhcBatch::Field fields[21] = {{S.qpos, n * nq}, {S.qvel, n * nv}, {S.xpos, n * 3 * nb}, {S.xquat, n * 4 * nb}, {S.xipos, n * 3 * nb}, {S.qM, n * A.t.nM}, {S.bias, n * nv},
                                         {S.qacc, n * nv}, {S.ctrl, n * nu}, {S.ncon, n}, {S.nefc, n}, {S.fail, n}, {S.solver_iter, n}, {S.applied, n * nv}, {S.overflow, n},
-                                        {S.prof, n * 40}, {S.redo, n}, {S.tier, n}, {S.why, n}};
-    std::copy(fields, fields + 19, b->field);
+                                        {S.prof, n * 40}, {S.redo, n}, {S.tier, n}, {S.why, n}, {S.qacc_ws, n * nv}, {S.cost, n}};
+    std::copy(fields, fields + 21, b->field);
     return 0;
 }
 
@@ -279,6 +280,7 @@ extern "C" int32_t uhc_batch_create(const UhcModel* const* models, int32_t n_mod
     b->use_fast = P.use_fast;
     b->hbm_guard = knobs.guard != 0;
     b->q2_div = knobs.q2_div; b->q2_wait_min = knobs.q2_wait_min; b->q2_max = knobs.q2_max; b->q3_max = knobs.q3_max; b->q4_max = knobs.q4_max;
+    b->fast_chunk = (P.A.dbg & 4) ? 0x7fff : knobs.fast_chunk;  // (UHC_DEBUG bit 2 restarts a handed-on env's step from substep 0: only the whole-step launch can)
     TRY(upload_plan(b, P, models[0]->d, ctrl, h_env_model));
     HIP_OK(uhc_set_lds_limit(b->lds_bytes, b->lds_bytes_fast, b->lds_bytes_big));
     TRY(alloc_state(b, models, h_env_model));
@@ -383,7 +385,7 @@ extern "C" int32_t uhc_batch_set_solver(UhcBatch* b, int32_t solver, int32_t ite
     return 0;
 }
 extern "C" int32_t uhc_batch_field(UhcBatch* b, int32_t f, void** p, int64_t* n) {
-    if (!b || f < 0 || f > 18 || !b->field[f].ptr) return fail("uhc_batch_field: unknown field %d", f);
+    if (!b || f < 0 || f > 20 || !b->field[f].ptr) return fail("uhc_batch_field: unknown field %d", f);
     if (p) *p = b->field[f].ptr;
     if (n) *n = b->field[f].count;
     return 0;
@@ -407,6 +409,7 @@ static int launch_sticky(UhcBatch* b, int mode, const double* d_action, const do
         (void)hipGetLastError();
     StickyInputs in{};
     in.est4 = est4; in.est2_then = est2_then; in.n_env = b->n_env; in.n_cu = b->n_cu; in.lds_bytes_fast = b->lds_bytes_fast; in.large_first = b->large_first;
+    in.fast_chunk = b->fast_chunk; in.n_substeps = b->A.c.n_substeps;
     in.last_tier = b->A.last_tier; in.q2_div = b->q2_div; in.q2_wait_min = b->q2_wait_min; in.q2_max = b->q2_max; in.q3_max = b->q3_max; in.q4_max = b->q4_max;
 #ifdef UHC_EXPERIMENTS
     in.fixed_cap2 = (b->A.dbg & 2048) != 0;  // (measurement switch: a fixed cap UHC_Q2_MAX on the general tier's consumers)
@@ -470,7 +473,7 @@ static int launch_sticky(UhcBatch* b, int mode, const double* d_action, const do
             if (q3 && b->large_first && !(b->A.dbg & 32)) HIP_OK(uhc_launch_gate(b->d_fin + 4, grid3, nullptr, nullptr, b->side_stream));
             K.tier_want = 0; K.list = b->d_lists; K.list_count = b->d_counts + 2; K.list_cursor = b->d_cursors + 2;
             K.grid = grid2;
-            K.prod_fin = waiting ? b->d_fin + 1 : nullptr; K.prod_total = b->n_env;  // every workgroup of the fast tier's launch below
+            K.prod_fin = waiting ? b->d_fin + 1 : nullptr; K.prod_total = z.fast.prod_total;  // every workgroup of the fast tier's launch below
             K.fin = b->d_fin + 2; K.started = waiting ? b->d_fin + 3 : nullptr;
             K.n_wait = z.n_wait; K.spares = b->d_fin;
             K.q_next = q3 ? b->d_lists + b->n_env : nullptr; K.q_next_count = q3 ? b->d_counts + 3 : nullptr;
@@ -485,13 +488,14 @@ static int launch_sticky(UhcBatch* b, int mode, const double* d_action, const do
         if (waiting && !(b->A.dbg & 32)) HIP_OK(uhc_launch_gate(b->d_fin + 3, grid2, b->d_counts + 1,
                                                                      (b->A.dbg & 16) ? b->A.s.prof + (size_t)(b->n_env - 1) * 40 + 16 : nullptr, b->stream));
         K.tier_want = 1;
+        K.chunk = z.fast.chunk; K.grid = z.fast.chunk ? z.fast.grid : 0;  // (in substep chunks: n_chunks x n_env workgroups, chunk-major by ticket)
         K.order = b->d_order;  // (costliest envs first; null with UHC_DEBUG bit 3: env order)
         K.fin = waiting ? b->d_fin + 1 : nullptr;
         K.q_next = waiting ? b->d_lists : nullptr; K.q_next_count = waiting ? b->d_counts + 2 : nullptr;
         if (timed) HIP_OK(hipEventRecord(ev.first, b->stream));
         HIP_OK(uhc_launch_step(mode, 1, &K, d_action, d_tbase, d_active, b->lds_bytes_fast, b->stream));
         if (timed) { HIP_OK(hipEventRecord(ev.second, b->stream)); b->ev_used.push_back(ev); }
-        K.tier_want = 0; K.sticky_mask = 0; K.fin = nullptr; K.q_next = nullptr; K.q_next_count = nullptr; K.order = nullptr;
+        K.tier_want = 0; K.sticky_mask = 0; K.fin = nullptr; K.q_next = nullptr; K.q_next_count = nullptr; K.order = nullptr; K.chunk = 0; K.grid = 0;
         // chained launches on what is still flagged: everything handed on when no consumers run, nothing (two empty launches) when they do
         if (queues) HIP_OK(hipStreamWaitEvent(b->stream, b->ev_side1, 0));
         HIP_OK(uhc_launch_step(mode, 2, &K, d_action, d_tbase, b->A.s.pend2, b->lds_bytes, b->stream));
@@ -518,7 +522,7 @@ static int launch(UhcBatch* b, int mode, const double* d_action, const double* d
     const bool general = b->general_only;
     const bool big = b->A.last_tier >= 3;  // (tier 4 has no chained launch of its own: the large tier's workgroups go on with it; under sticky tiers it has queue consumers)
     // tier chain: every tier works on the envs the previous one flagged (redo / redo2) and left untouched
-    HIP_OK(hipMemsetAsync(b->A.s.redo, 0, sizeof(int) * b->n_env * 5, b->stream));  // redo (the step's UHC_F_REDO words), pend2, pend3, resume, why: one allocation
+    HIP_OK(hipMemsetAsync(b->A.s.redo, 0, sizeof(int) * ((size_t)b->n_env * 6 + 1), b->stream));  // redo (the step's UHC_F_REDO words), pend2, pend3, resume, why, chunk_done, ticket: one allocation
     // (inside a stream capture the sticky launch cannot be used: it sizes its consumer launches from counts the host reads between steps
     //  -- event queries and a wait that are not allowed while capturing, and a replay would repeat the capture step's sizes anyway.  A
     //  captured step takes the plain tier chain, which computes the same step.)
@@ -531,7 +535,12 @@ static int launch(UhcBatch* b, int mode, const double* d_action, const double* d
     if (mode == 0 && b->path_mode == 2 && b->use_fast && !general && !capturing) return launch_sticky(b, mode, d_action, d_tbase, d_active, timed, ev);
     if (b->use_fast && !general) {
         if (timed) HIP_OK(hipEventRecord(ev.first, b->stream));
-        HIP_OK(uhc_launch_step(mode, 1, &b->A, d_action, d_tbase, d_active, b->lds_bytes_fast, b->stream));
+        KernelArgs K = b->A;
+        if (mode == 0) {  // the control step in substep chunks (the forward-only and kinematics launches have no substeps)
+            const FastChunks f = plan_fast_chunks(K.c.n_substeps, default_fast_chunk(b->fast_chunk, K.c.n_substeps, b->n_env, b->n_cu, b->lds_bytes_fast), b->n_env);
+            K.chunk = f.chunk; K.grid = f.chunk ? f.grid : 0;
+        }
+        HIP_OK(uhc_launch_step(mode, 1, &K, d_action, d_tbase, d_active, b->lds_bytes_fast, b->stream));
         if (timed) { HIP_OK(hipEventRecord(ev.second, b->stream)); b->ev_used.push_back(ev); }
         HIP_OK(uhc_launch_step(mode, 2, &b->A, d_action, d_tbase, b->A.s.pend2, b->lds_bytes, b->stream));
     } else {
@@ -566,6 +575,17 @@ extern "C" int32_t uhc_batch_kernel_time(UhcBatch* b, double* total_ms, int32_t*
     *total_ms = tot;
     *launches = (int32_t)b->ev_used.size();
     b->ev_used.clear();
+    return 0;
+}
+
+extern "C" int32_t uhc_batch_give_ups(UhcBatch* b, int32_t* n, int32_t* n_slow) {
+    if (!b || !n) return fail("uhc_batch_give_ups: null argument");
+    HIP_OK(hipSetDevice(b->device));
+    HIP_OK(hipStreamSynchronize(b->stream));
+    int v[2] = {0, 0};
+    HIP_OK(hipMemcpy(v, b->A.s.q_abort, sizeof v, hipMemcpyDeviceToHost));
+    *n = v[0];
+    if (n_slow) *n_slow = v[1];
     return 0;
 }
 

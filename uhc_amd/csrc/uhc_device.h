@@ -116,7 +116,7 @@ struct DevState {  // HBM, env-major
     int* why;            // diagnostic (UHC_F_HANDON_WHY): bits 0-7 why the fast tier handed the env on in this step, bits 8-15 why the general tier did
                          // (1 contacts, 2 rows, 4 body-body row slots, 8 packed row storage, 16 MPR candidate list), bits 16+ the substep of the last hand-on
     int* resume;         // substep at which the tier below handed the env on (its state then is in qpos / qvel / qacc_ws / ctrl / applied); 0: from the start
-    int* q_abort;  // consumers that gave up waiting for their producers (queue_claim)
+    int* q_abort;  // [0] consumers that gave up waiting for producers of which none had finished (queue_claim: the host backs off), and chunk waiters; [1] consumers that left behind producers that were running but slow (reported, not acted on)
     int* tier;   // per env: the tier that computed its last control step (minus hysteresis): where its next step starts (kernel path 2)
     const int* tier_now;  // snapshot of `tier` taken at the head of the step: what the tier filter of a launch reads
     int* cost;   // per env: how close its last step came to the fast tier's capacity, in sixty-fourths (orders the fast tier's launch)
@@ -206,4 +206,17 @@ struct KernelArgs {
     DevCtrl c;
     DevState s;
     int n_env;
+    // the fast tier's control step in substep chunks (uhc_step_kernel<0, 1, *>): n_chunks x n_env workgroups, each runs `chunk` substeps of one env
+    int chunk;        // substeps per chunk (0: one workgroup runs the env's whole step, blockIdx = place in the launch order)
+    int* ticket;      // the launch's ticket counter: ticket = chunk index * n_env + place in the launch order (reset on the stream before every launch)
+    int* chunk_done;  // per env: chunks of this step that are finished and stored (UHC_CHUNK_ALL: the fast tier's step is over -- last chunk done, bad value or
+                      // hand-on); UHC_CHUNK_CLOSING: its holder has done the chunk's last substep; UHC_CHUNK_ABANDON: a workgroup gave up waiting for the env; UHC_CHUNK_TAKEN: its holder runs the rest of the step itself
+    int* chunk_rec;   // per env UHC_CHUNK_REC ints: what the step's later chunks need of the earlier ones beside the state (words below)
 };
+#define UHC_CHUNK_ALL 0x7fff
+#define UHC_CHUNK_ABANDON (1 << 30)
+#define UHC_CHUNK_TAKEN (1 << 29)
+#define UHC_CHUNK_CLOSING (1 << 28)
+#define UHC_CHUNK_REC 16
+// chunk_rec words: 0-4 the peaks of the step's substeps so far (rows, contacts, body-body rows, packed Yhat entries, force-carrying rows: they decide the env's
+// next tier and its place in the launch order), 5-7 ncon / nefc / solver_iter of its newest forward pass, 8 the truncation bits

@@ -51,6 +51,7 @@ struct UhcBatch {
     int q2_max = 256;        // most general-tier consumers beside a fast tier that still has most of the envs (UHC_Q2_MAX)
     int q4_max = 16;         // most tier-4 consumers (UHC_Q4_MAX; 0: none -- what the large tier hands on waits for the chained launch at the end of the step)
     int q3_max = 32;         // most large-tier consumers in that regime (UHC_Q3_MAX)
+    int fast_chunk = 0;      // substeps per chunk of the fast tier's control step (UHC_FAST_CHUNK; 0: default_fast_chunk decides)
     int *d_lists = nullptr, *d_counts = nullptr, *d_cursors = nullptr, *d_fin = nullptr;
     bool queues_off = false;
     int* h_counts = nullptr;  // pinned [8][8]: give-ups, gate wait, final queue lengths [2], [3], queue lengths at the head of the step [4], [5]; the last steps', copied back asynchronously
@@ -65,5 +66,5 @@ struct UhcBatch {
     int n_trailing_free = 0;  // free bodies at the end of the model (objects)
     bool hbm_guard = false;  // UHC_GUARD_LDS=1 / 2: zero-initialised device arrays sit between fences (dalloc)
     struct Field { void* ptr; int64_t count; };
-    Field field[19] = {};  // uhc_batch_field: UHC_F_* -> (device pointer, elements)
+    Field field[21] = {};  // uhc_batch_field: UHC_F_* -> (device pointer, elements)
 };

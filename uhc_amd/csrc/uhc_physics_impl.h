@@ -2816,9 +2816,28 @@ __device__ __forceinline__ void k_rfc_explicit(const KernelArgs& A, double* S, c
 // launches the general variant on exactly those envs.
 // DENSE: the model has contacts between two moving bodies (convex-convex pairs): MPR narrow phase + dense rows are compiled in.  The
 // floor-only stock model runs the DENSE = false instantiation, whose code and register allocation are those of the kernel without them.
+__device__ __forceinline__ int chunk_rec_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// The chunked fast tier's progress word (KernelArgs::chunk_done), lane 0 of the workgroup that holds the env, behind the last substep of a chunk that
+// does not end the step.  -> false: the chunk is CLOSING -- from here no waiter gives the env up any more, the count follows behind the chunk's stores;
+// -> true: a waiter has given the env up (UHC_CHUNK_ABANDON): it is marked UHC_CHUNK_TAKEN in the same atomic and this workgroup runs the rest of the step.
+__device__ __forceinline__ bool chunk_closing(const KernelArgs& A, const int env) {
+    int v = __hip_atomic_load(A.chunk_done + env, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        const bool mine = (v & UHC_CHUNK_ABANDON) != 0;
+        if (__hip_atomic_compare_exchange_strong(A.chunk_done + env, &v, v | (mine ? UHC_CHUNK_TAKEN : UHC_CHUNK_CLOSING), __ATOMIC_ACQ_REL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return mine;
+    }
+}
 // returns 1 when the env was handed on to the next tier (nothing committed; the large tier's workgroup then goes on with it as tier 4), else 0
+// The fast tier's control step (MODE 0, TIER 1) also runs as a CHUNK of substeps [lo, hi): nothing lives across a substep boundary but what the step stores at
+// its end and loads at its start, so a chunk boundary is that store followed by that load -- the same operations on the same doubles.  What the step's
+// epilogue needs of the earlier chunks (the peaks, the counts of the newest forward pass, the truncation bits) is in the env's record KernelArgs::chunk_rec:
+// lane 0 merges it in at the two ends of a chunk, nothing of it is kept in registers across the substeps.  A chunk that ends before the step does returns 2
+// with the state and the record stored; a bad value or a hand-on ends the step in whatever chunk meets it, exactly as it ends the whole-step form.
+// (lo = 0, hi >= n_substeps: the whole step.)
 template <int MODE, int TIER, bool DENSE>
-__device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* __restrict__ d_action, const double* __restrict__ d_tbase, const int env) {
+__device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* __restrict__ d_action, const double* __restrict__ d_tbase, const int env,
+                                            const int lo = 0, const int hi = 0x7fffffff) {
+    constexpr bool CH = MODE == 0 && TIER == 1;  // (every other instantiation: lo and hi are compiled out)
     const DevTopo& T = A.t;
     const DevLds& L = lds_of<TIER>(A);
     double* S = smem;
@@ -2834,7 +2853,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
 #else
 #define TRACE(slot, v)
 #endif
-    TRACE(2 * (TIER - 1), wall_clock64())
+    if (!CH || lo == 0) { TRACE(2 * (TIER - 1), wall_clock64()) }
     int fail = MODE == 0 ? A.s.fail[env] : 0;
     // A tier that finds an env too big in substep k >= 1 hands it on WITH the substeps it has done: the state at the start of substep k
     // (qpos, qvel, warm start) and that substep's controls (ctrl, applied: PD torque and residual force are already computed) are in
@@ -2843,7 +2862,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
     // (read past the scalar cache: `env` is wave-uniform, and a consumer workgroup that lives through many envs of a launch must not meet a
     //  line another wave fetched before the tier below wrote its word)
     const int res = (MODE == 0 && TIER != 1) ? __hip_atomic_load(A.s.resume + env, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    const bool fresh = MODE == 0 && res == 0 && A.s.fresh[env] != 0;  // restarted by uhc_env_auto_reset: sim.forward() of the reset is still due
+    const bool fresh = MODE == 0 && res == 0 && (!CH || lo == 0) && A.s.fresh[env] != 0;  // restarted by uhc_env_auto_reset: sim.forward() of the reset is still due
     // ---- load state (coalesced: consecutive lanes, consecutive doubles)
     for (int i = LANE; i < T.nq; i += UHC_WAVE) S[L.qpos + i] = A.s.qpos[(size_t)env * T.nq + i];
     for (int i = LANE; i < T.nv; i += UHC_WAVE) {
@@ -2888,8 +2907,11 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
     FwdOut fo = {0, 0, 0, 0, 0, 0};
     int it = 0;
     int overflow = 0, swept = 0;  // swept: bit 8 + k = substep k of this step was solved by the sweeps (general kernel, solver 1)
-    bool ran = false, fits = true;  // fits (general / large tier): every substep of this step was within the fast kernel's capacity
-    int pk_nefc = 0, pk_ncon = 0, pk_ntwo = 0, pk_y = 0, pk_act = 0;  // the step's peaks over its substeps: rows, contacts, body-body rows, packed Yhat entries (sticky tiers)
+    bool ran = false, fits = true;  // (ran: a forward pass ran in THIS invocation; a later chunk of a step also has those of the earlier chunks behind it: ran_step below)
+    // fits (general / large tier): every substep of this step was within the fast kernel's capacity
+    int pk_nefc = 0, pk_ncon = 0, pk_ntwo = 0, pk_y = 0, pk_act = 0;
+    int it_end = A.c.n_substeps;  // (a chunk: min(hi, n_substeps), raised to n_substeps when a waiter has given the env up: chunk_closing)
+    // the step's peaks over its substeps: rows, contacts, body-body rows, packed Yhat entries (sticky tiers)
     PROF_DECL
     if (MODE == 2) {  // kinematics of a device-side restart: what the reset observation reads; the rest of sim.forward() is deferred
         k_kinematics<TIER>(A, mb, S, BC PROF_PASS);
@@ -2919,7 +2941,8 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
         const double* tbase = d_tbase + (size_t)env * T.nu;
         // a freshly restarted env first runs the forward pass of its reset (it = -1: no control, no integration), through the
         // same inlined k_forward as the substeps
-        for (it = fresh ? -1 : res; it < A.c.n_substeps; it++) {
+        if (CH) it_end = min(hi, A.c.n_substeps);
+        for (it = fresh ? -1 : (CH ? lo : res); it < it_end; it++) {
             int b = 0;
             if (it >= 0) {
             if (!(res > 0 && it == res)) {  // (the controls of the substep an env was handed on in came with it)
@@ -2965,6 +2988,11 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
             if (T.has_damping) { k_damped_accel<TIER>(A, mb, S, MP, LC); k_euler<TIER>(A, S, L.smooth); }
             else k_euler<TIER>(A, S, L.qacc);
             PROF(14)
+            if (CH && it + 1 == it_end && it_end < A.c.n_substeps) {  // the last substep of a chunk that does not end the step: close the chunk, or go on if a waiter gave the env up
+                int mine = 0;
+                if (LANE == 0) mine = chunk_closing(A, env) ? 1 : 0;
+                if (__builtin_amdgcn_readfirstlane(mine)) it_end = A.c.n_substeps;
+            }
         }
     }
     if (overflow & 1) {  // nothing committed: the next tier takes the env over -- from the substep that did not fit, or from the same inputs
@@ -3001,27 +3029,32 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
         return 1;
     }
     guard_check<TIER>(A, S, env, 0);
+    const bool ran_step = ran || (CH && lo > 0);  // a forward pass ran in this control step (a chunk >= 1 has those of the earlier chunks behind it)
     // ---- store state
     for (int i = LANE; i < T.nq; i += UHC_WAVE) A.s.qpos[(size_t)env * T.nq + i] = S[L.qpos + i];
     for (int i = LANE; i < T.nv; i += UHC_WAVE) {
         A.s.qvel[(size_t)env * T.nv + i] = S[L.qvel + i];
         A.s.qacc[(size_t)env * T.nv + i] = S[L.qacc + i];
-        if (MODE == 0 && ran) A.s.qacc_ws[(size_t)env * T.nv + i] = S[L.qacc + i];  // mj_forward alone leaves the warm start
+        if (MODE == 0 && ran_step) A.s.qacc_ws[(size_t)env * T.nv + i] = S[L.qacc + i];  // mj_forward alone leaves the warm start
         A.s.applied[(size_t)env * T.nv + i] = S[L.applied + i];
     }
     for (int i = LANE; i < T.nu; i += UHC_WAVE) A.s.ctrl[(size_t)env * T.nu + i] = S[L.ctrl + i];
-    if (ran) {
+    if (ran_step) {
         for (int i = LANE; i < T.nv; i += UHC_WAVE) A.s.bias[(size_t)env * T.nv + i] = S[L.bias + i];
 #pragma unroll
         for (int m = 0; m < UHC_MREG; m++) {
             const int e = LANE + UHC_WAVE * m;
             if (e < T.nM) A.s.qM[(size_t)env * T.nM + e] = __hiloint2double(agpr_get(MP.hi[m]), agpr_get(MP.lo[m]));
         }
+        // (the body poses are in LDS only behind a forward pass of THIS invocation: a chunk >= 1 that a bad value ends at the head of its first substep has
+        //  loaded none -- xipos never, xpos / xquat for explicit RFC alone -- and the poses of the step's newest forward pass are what the previous chunk stored)
+        if (!CH || ran) {
         for (int i = LANE; i < 3 * T.nbody; i += UHC_WAVE) {
             A.s.xpos[(size_t)env * 3 * T.nbody + i] = S[L.xpos + i];
             A.s.xipos[(size_t)env * 3 * T.nbody + i] = S[L.xipos + i];
         }
         for (int i = LANE; i < 4 * T.nbody; i += UHC_WAVE) A.s.xquat[(size_t)env * 4 * T.nbody + i] = S[L.xquat + i];
+        }
         if (A.c.rfc_mode == 2) {
             for (int i = LANE; i < 6 * T.nv; i += UHC_WAVE) A.s.cdof[(size_t)env * 6 * T.nv + i] = S[L.cdof + i];
             for (int i = LANE; i < 3 * T.nbody; i += UHC_WAVE) A.s.rootcom[(size_t)env * 3 * T.nbody + i] = S[L.rootcom + i];
@@ -3036,6 +3069,17 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
         if (LANE < UHC_NPROF) A.s.prof[(size_t)env * UHC_NPROF + LANE] += mine;
     }
 #endif
+    if (CH && !fail && it_end < A.c.n_substeps) {  // the end of a chunk, not of the step: the next chunk's workgroup goes on from the state just stored
+        if (LANE == 0) {  // the record: peaks and truncation bits merged with the earlier chunks', the counts of the newest forward pass (this chunk's)
+            int* rec = A.chunk_rec + (size_t)env * UHC_CHUNK_REC;
+            if (lo > 0) {  // (words another workgroup wrote during this launch: read past the scalar cache, like `resume`)
+                pk_nefc = max(pk_nefc, chunk_rec_load(rec + 0)); pk_ncon = max(pk_ncon, chunk_rec_load(rec + 1)); pk_ntwo = max(pk_ntwo, chunk_rec_load(rec + 2));
+                pk_y = max(pk_y, chunk_rec_load(rec + 3)); pk_act = max(pk_act, chunk_rec_load(rec + 4)); overflow |= chunk_rec_load(rec + 8);
+            }
+            rec[0] = pk_nefc; rec[1] = pk_ncon; rec[2] = pk_ntwo; rec[3] = pk_y; rec[4] = pk_act; rec[5] = fo.ncon; rec[6] = fo.nefc; rec[7] = fo.iters; rec[8] = overflow;
+        }
+        return 2;
+    }
     TRACE(2 * (TIER - 1) + 1, wall_clock64())
     double vmax_end = 0.0;  // largest |qvel| at the end of the step (the launch order of the next one)
     if (MODE == 0) {
@@ -3043,7 +3087,13 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
         vmax_end = -wave_min(-vmax_end);
     }
     if (LANE == 0) {
-        if (ran) { A.s.ncon[env] = fo.ncon; A.s.nefc[env] = fo.nefc; A.s.solver_iter[env] = fo.iters; }
+        if (CH && lo > 0) {  // the step's earlier chunks (their record, read past the scalar cache)
+            const int* rec = A.chunk_rec + (size_t)env * UHC_CHUNK_REC;
+            pk_nefc = max(pk_nefc, chunk_rec_load(rec + 0)); pk_ncon = max(pk_ncon, chunk_rec_load(rec + 1)); pk_ntwo = max(pk_ntwo, chunk_rec_load(rec + 2));
+            pk_y = max(pk_y, chunk_rec_load(rec + 3)); pk_act = max(pk_act, chunk_rec_load(rec + 4)); overflow |= chunk_rec_load(rec + 8);
+            if (!ran) { fo.ncon = chunk_rec_load(rec + 5); fo.nefc = chunk_rec_load(rec + 6); fo.iters = chunk_rec_load(rec + 7); }  // (a bad value at the head of the chunk's first substep)
+        }
+        if (ran_step) { A.s.ncon[env] = fo.ncon; A.s.nefc[env] = fo.nefc; A.s.solver_iter[env] = fo.iters; }
         A.s.fail[env] = fail;
         if (overflow & 3) A.s.overflow[env] = 1;
         A.s.fresh[env] = 0;
@@ -3054,7 +3104,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
         // longer fits costs that tier's work so far, and the step then ends a whole general- (or large-) tier env-step after the moment
         // of the hand-on -- with a thousand envs some env does that every step, and every step lasts fast + general + large.  It comes
         // down again only well below the mark (hysteresis).  The marks are the batch's (KernelArgs::marks, UHC_TIER_MARKS).
-        if (MODE == 0 && ran) {
+        if (MODE == 0 && ran_step) {
             const int* mk = A.marks;  // up2: rows, contacts, body-body rows | dn1: the same | up3, dn2: eighths of the general tier's capacities
             const bool up2 = pk_nefc > mk[0] || pk_ncon > mk[1] || pk_ntwo > mk[2];   // of 64 rows / 16 contacts / 12 body-body rows
             // (... and only if its packed rows fit the fast tier's storage: with objects in the model that storage is small, and an env that
@@ -3137,18 +3187,87 @@ __device__ __forceinline__ int queue_claim(const KernelArgs& A, int& role, const
         // launches, and the host stops starting consumers when it sees the count (DevState::q_abort).
         // (quiet: tier 4's consumers -- they wait behind the large tier's, which in a step of the general tier's majority regime may last longer than that
         //  without anything being wrong; when one leaves, what is handed on later stays flagged for the chained launch as well)
-        if (wall_clock64() - t0 > 5000000ull) { if (!quiet) atomicAdd(A.s.q_abort, 1); return -1; }
+        // (counted only while NO producer has finished: the count is the host's sign that the producers' launch does not run beside this one, and it turns the
+        //  queues off for the next steps.  Producers that have begun to finish do run beside it; one of them working for more than 50 ms on a heavy env -- a
+        //  general-tier consumer on a diverging humanoid, with the large tier's spares waiting behind it -- is slow, not stuck, and the spare just leaves)
+        if (wall_clock64() - t0 > 5000000ull) { if (!quiet) atomicAdd(A.s.q_abort + (f == 0 ? 0 : 1), 1); return -1; }  // ([1]: behind SLOW producers; the host does not act on it, uhc_batch_give_ups reports it)
         __builtin_amdgcn_s_sleep(64);
     }
+}
+// The fast tier's control step in substep chunks (KernelArgs::chunk > 0).  One workgroup per (chunk, env): the whole-step launch deals the chip's
+// places out an env-step at a time, and whatever does not fit its first round starts when the first envs leave -- a second round in which most places stand
+// empty.  Dealt out a chunk at a time the same work keeps them full.  A workgroup takes a TICKET (dispatch order is not relied on): chunk-major, the launch
+// order inside a chunk.  Every lower ticket belongs to a workgroup that is resident already, so waiting for the env's previous chunk cannot deadlock.
+// chunk_wait (lane 0): until `c` chunks of the env are done -> 1; the env's step is over (bad value, hand-on) or its holder goes on with it -> 0.  Bounded like
+// queue_claim: after 50 ms the workgroup flags the env UHC_CHUNK_ABANDON -- one compare-and-swap, which fails once the holder has marked its chunk
+// UHC_CHUNK_CLOSING (chunk_closing) --, counts itself in q_abort and leaves for good.  The holder meets the flag behind the last substep of its chunk, marks
+// the env UHC_CHUNK_TAKEN in the same atomic and runs the rest of the step itself, inside its substep loop: no substep is dropped whoever gives up, no chunk
+// runs twice.  (The env is not passed to the general tier: the holder is the only party that knows the state, and `resume` promises the controls of the substep,
+// which do not exist yet at a chunk boundary.)  A waiter that finds the chunk CLOSING at its time-out waits on: the holder is alive and only has the
+// chunk's stores left.  Should it not publish within another 50 ms the waiter counts itself and leaves -- that holder is lost, and the state with it.
+__device__ __forceinline__ int chunk_wait(const KernelArgs& A, const int env, const int c) {
+    unsigned long long t0 = wall_clock64();  // 100 MHz
+    const unsigned long long t_in = t0;
+    int r, late = 0;
+    for (;;) {
+        int v = __hip_atomic_load(A.chunk_done + env, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        if ((v & 0xffff) == UHC_CHUNK_ALL || (v & UHC_CHUNK_TAKEN)) { r = 0; break; }
+        if ((v & 0xffff) >= c) { r = 1; break; }
+        if (wall_clock64() - t0 > 5000000ull) {
+            if (!(v & UHC_CHUNK_CLOSING) && !(v & UHC_CHUNK_ABANDON) &&
+                !__hip_atomic_compare_exchange_strong(A.chunk_done + env, &v, v | UHC_CHUNK_ABANDON, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;  // (it moved: look again)
+            if ((v & UHC_CHUNK_CLOSING) && !late) { late = 1; t0 = wall_clock64(); continue; }
+            atomicAdd(A.s.q_abort, 1);
+            r = 0;
+            break;
+        }
+        __builtin_amdgcn_s_sleep(32);
+    }
+#ifndef UHC_STAGE_PROF
+    if (A.dbg & 16) A.s.prof[(size_t)env * UHC_NPROF + 24] += (long long)(wall_clock64() - t_in);  // tier trace: ticks the env's chunks spent waiting (the tool clears the record per step)
+#endif
+    return r;
 }
 template <int MODE, int TIER, bool DENSE>
 __global__ void __launch_bounds__(UHC_WAVE) uhc_step_kernel(KernelArgs A, const double* __restrict__ d_action,
                                                             const double* __restrict__ d_tbase, const int* __restrict__ d_active) {
-    const int env = (A.order && (int)blockIdx.x < A.n_env) ? A.order[blockIdx.x] : (int)blockIdx.x;
+    int place = (int)blockIdx.x, c = 0;
+    if constexpr (MODE == 0 && TIER == 1) {
+        if (A.chunk > 0) {
+            int tk = 0;
+            if (LANE == 0) tk = atomicAdd(A.ticket, 1);
+            tk = __builtin_amdgcn_readfirstlane(tk);
+            c = tk / A.n_env;
+            place = tk - c * A.n_env;
+        }
+    }
+    const int env = (A.order && place < A.n_env) ? A.order[place] : place;
     bool go = env >= 0 && env < A.n_env && !(d_active && !d_active[env]);  // (env < 0: a free slot of a list launch, A.order)
     if (go && A.tier_want) {  // sticky tiers: the envs whose tier has its own launch this step are not this launch's
         const int t = A.s.tier_now[env];
         go = t == A.tier_want || !((A.sticky_mask >> t) & 1);
+    }
+    if constexpr (MODE == 0 && TIER == 1) {
+        // (every chunk of an env evaluates the same filter on the same snapshot: d_active, tier_now and the mask do not change during the launch)
+        if (go && c > 0) {
+            int w = 0;
+            if (LANE == 0) w = chunk_wait(A, env, c);
+            w = __builtin_amdgcn_readfirstlane(w);
+            go = w != 0;
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (every lane: the state the previous chunk stored is loaded behind this)
+        }
+        if (go) {
+            const int lo = A.chunk > 0 ? c * A.chunk : 0, hi = A.chunk > 0 ? lo + A.chunk : 0x7fffffff;
+            const int r = uhc_step_env<MODE, TIER, DENSE>(A, d_action, d_tbase, env, lo, hi);
+            if (A.chunk > 0) {
+                __threadfence();  // (every lane's stores of the state, and lane 0's of the record, before the progress word)
+                // r == 2: chunk c is done and stored (the count also takes UHC_CHUNK_CLOSING back); else the env's fast-tier step is over -- its last chunk, a bad
+                // value or a hand-on -- and the workgroups of its later chunks leave at once
+                if (LANE == 0) __hip_atomic_store(A.chunk_done + env, r == 2 ? c + 1 : UHC_CHUNK_ALL, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        if (A.fin && LANE == 0) { __threadfence(); atomicAdd(A.fin, 1); }
+        return;
     }
     if (go) {
 #ifdef UHC_WITH_TIER4

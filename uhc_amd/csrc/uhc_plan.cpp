@@ -43,6 +43,12 @@ BatchKnobs read_knobs() {
     k.tiers = is("UHC_TIERS", '2') ? 2 : is("UHC_TIERS", '3') ? 3 : 0;
     at_least("UHC_Q2_DIV", 1, &k.q2_div); at_least("UHC_Q2_WAIT", 1, &k.q2_wait_min); at_least("UHC_Q2_MAX", 16, &k.q2_max);
     at_least("UHC_Q3_MAX", 2, &k.q3_max); at_least("UHC_Q4_MAX", 0, &k.q4_max); at_least("UHC_T4_ROWS", 0, &k.t4_rows);
+    if (const char* fc = getenv("UHC_FAST_CHUNK")) {  // (strict: a typo must not silently select the default)
+        char* end = nullptr;
+        const long v = strtol(fc, &end, 10);
+        if (end == fc || *end != 0 || v < 0) k.fast_chunk_bad = true;
+        else k.fast_chunk = (v == 0 || v > 0x7fff) ? 0x7fff : (int)v;
+    }
     return k;
 }
 
@@ -598,6 +604,7 @@ int plan_batch(const UhcModel* const* models, int n_models, const int32_t* env_m
                BatchPlan* out, std::string* err) {
     BatchPlan& P = *out;
     P = BatchPlan();
+    if (knobs.fast_chunk_bad) return refuse(err, "uhc_batch_create: UHC_FAST_CHUNK must be a non-negative integer (substeps per chunk of the fast tier's control step)");
     PLAN_TRY(validate(models, n_models, env_model, n_env, ctrl, &P.n_trailing_free, err));
     const UhcModelDesc& d = models[0]->d;
     KernelArgs& A = P.A;
@@ -638,9 +645,32 @@ int plan_batch(const UhcModel* const* models, int n_models, const int32_t* env_m
     return 0;
 }
 
+// ------------------------------------------------------------------ the fast tier's launch in substep chunks
+FastChunks plan_fast_chunks(int n_substeps, int chunk, int n_env) {
+    FastChunks f;
+    f.chunk = (chunk <= 0 || chunk >= n_substeps) ? 0 : chunk;
+    f.n_chunks = f.chunk ? (n_substeps + f.chunk - 1) / f.chunk : 1;
+    f.grid = f.n_chunks * n_env;
+    f.prod_total = f.grid;
+    return f;
+}
+void fast_chunk_range(const FastChunks& f, int n_substeps, int c, int* lo, int* hi) {
+    *lo = f.chunk ? c * f.chunk : 0;
+    *hi = f.chunk ? std::min(*lo + f.chunk, n_substeps) : n_substeps;
+}
+// UHC_FAST_CHUNK_DEFAULT substeps where the launch does not fit the chip at once: what does not fit starts when the first envs leave, a second round that
+// leaves most places empty.  A batch that fits in one round gains nothing from chunks and pays their boundaries: the whole-step launch.
+#define UHC_FAST_CHUNK_DEFAULT 5
+int default_fast_chunk(int knob, int n_substeps, int n_env, int n_cu, size_t lds_bytes_fast) {
+    if (knob > 0) return knob >= n_substeps ? 0 : knob;
+    const int per_cu = std::max(1, std::min(4, (int)(160 * 1024 / std::max<size_t>(lds_bytes_fast, 1))));
+    return (n_env > per_cu * n_cu && UHC_FAST_CHUNK_DEFAULT < n_substeps) ? UHC_FAST_CHUNK_DEFAULT : 0;
+}
+
 // ------------------------------------------------------------------ sticky tiers: one step's consumer launches
 StickySizes plan_sticky_step(const StickyInputs& in) {
     StickySizes s;
+    s.fast = plan_fast_chunks(in.n_substeps, in.n_substeps > 0 ? default_fast_chunk(in.fast_chunk, in.n_substeps, in.n_env, in.n_cu, in.lds_bytes_fast) : 0, in.n_env);
     const int est2 = in.est2, est3 = in.est3, est4 = in.est4, n_env = in.n_env, n_cu = in.n_cu;
     const bool big = in.last_tier >= 3;  // (tier 4 has no chained launch of its own: the large tier's workgroups go on with it; under sticky tiers it has queue consumers)
     s.launch4 = in.last_tier == 4 && est4 > 0 && in.est2_then > 0 && big && !in.queues_off;  // (the list kernel's view; the consumers need the large tier's beside them: q4 below)

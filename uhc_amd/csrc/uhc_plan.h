@@ -19,6 +19,9 @@ struct BatchKnobs {
     int guard = 0;                  // UHC_GUARD_LDS: 1 guard words, 2 the self-test (one guard ON qpos of the fast tier), 0 off
     int q2_div = 1, q2_wait_min = 16, q2_max = 256, q3_max = 32, q4_max = 16;  // UHC_Q2_DIV >= 1, UHC_Q2_WAIT >= 1, UHC_Q2_MAX >= 16, UHC_Q3_MAX >= 2, UHC_Q4_MAX >= 0
     int t4_rows = 0;                // UHC_T4_ROWS >= 0
+    int fast_chunk = 0;             // UHC_FAST_CHUNK=<substeps>: the fast tier's control step runs in chunks of so many substeps (0: not given, default_fast_chunk
+                                    // decides; a value >= n_substeps, and "0" itself, mean one chunk: the whole-step launch)
+    bool fast_chunk_bad = false;    // ... was given and is not a non-negative integer: plan_batch refuses the batch
 };
 BatchKnobs read_knobs();
 
@@ -54,9 +57,23 @@ struct StickyInputs {
     bool queues_off;       // no waiting consumers (back-off after a consumer gave up)
     int q2_div, q2_wait_min, q2_max, q3_max, q4_max;
     bool fixed_cap2;       // measurement switch (UHC_DEBUG bit 11 of -DUHC_EXPERIMENTS builds): a fixed cap UHC_Q2_MAX on the general tier's consumers
+    int fast_chunk;        // BatchKnobs::fast_chunk (0: the default), and the control step's substeps (0: the fast tier's launch is not chunked)
+    int n_substeps;
 };
+// the fast tier's launch in substep chunks (uhc_step_kernel<0, 1, *>): chunk c of an env runs the substeps [c chunk, min((c + 1) chunk, n_substeps))
+struct FastChunks {
+    int chunk;       // substeps per chunk; 0: one workgroup per env runs the whole step (KernelArgs::chunk)
+    int n_chunks;
+    int grid;        // workgroups of the launch: n_chunks x n_env
+    int prod_total;  // what the general tier's consumers wait for: every workgroup of the launch
+};
+FastChunks plan_fast_chunks(int n_substeps, int chunk, int n_env);  // chunk <= 0 or >= n_substeps: one chunk
+void fast_chunk_range(const FastChunks& f, int n_substeps, int c, int* lo, int* hi);
+// the chunk size of a launch: the knob when given, else by whether the batch fills the chip's places for fast-tier workgroups more than once
+int default_fast_chunk(int knob, int n_substeps, int n_env, int n_cu, size_t lds_bytes_fast);
 struct StickySizes {
     bool queues, waiting, q3, q4, launch4;
     int grid2, grid3, grid4, n_wait, sticky_mask;
+    FastChunks fast;
 };
 StickySizes plan_sticky_step(const StickyInputs& in);

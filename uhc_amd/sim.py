@@ -14,7 +14,8 @@ from ._lib import check, lib
 
 F_QPOS, F_QVEL, F_XPOS, F_XQUAT, F_XIPOS, F_QM, F_QFRC_BIAS, F_QACC, F_CTRL = range(9)
 F_NCON, F_NEFC, F_FAIL, F_SOLVER_ITER, F_QFRC_APPLIED, F_EFC_OVERFLOW, F_STAGE_PROF, F_REDO, F_TIER, F_HANDON_WHY = range(9, 19)
-_INT_FIELDS = {F_NCON, F_NEFC, F_FAIL, F_SOLVER_ITER, F_EFC_OVERFLOW, F_REDO, F_TIER, F_HANDON_WHY}
+F_QACC_WARMSTART, F_COST = 19, 20
+_INT_FIELDS = {F_NCON, F_NEFC, F_FAIL, F_SOLVER_ITER, F_EFC_OVERFLOW, F_REDO, F_TIER, F_HANDON_WHY, F_COST}
 
 
 class _DevView:
@@ -176,6 +177,18 @@ class SimBatch:
         ms, n = C.c_double(), C.c_int32()
         check(self.L.uhc_batch_kernel_time(self._b, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    def give_ups(self) -> int:
+        """Workgroups that gave up waiting (queue consumers, chunk waiters) since the batch was created; 0 in a healthy run."""
+        n = C.c_int32()
+        check(self.L.uhc_batch_give_ups(self._b, C.byref(n), None))
+        return n.value
+
+    def slow_leaves(self) -> int:
+        """Queue consumers that left after 50 ms behind producers that were running but had not all finished (a very slow env-step in the tier below)."""
+        n, m = C.c_int32(), C.c_int32()
+        check(self.L.uhc_batch_give_ups(self._b, C.byref(n), C.byref(m)))
+        return m.value
 
 
 E_OBS, E_REWARD, E_REWARD_PARTS, E_DONE, E_FAIL, E_END, E_PERCENT, E_CUR_T, E_BODY_DIFF, E_TARGET_BASE, E_CONSUMED, E_EPISODE, E_SNAPSHOT = range(13)
