@@ -29,7 +29,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define UHC_ABI_VERSION 10  /* 10: uhc_build_flags; 9: UHC_F_REDO bits 29 / 30 (tier 4), swept-substep bits 8 .. 28; uhc_rollout_record counts int64 [7] */
+#define UHC_ABI_VERSION 11  /* 11: uhc_expert_frames (the clip bank's frame records computed on the device); 10: uhc_build_flags; 9: UHC_F_REDO bits 29 / 30 (tier 4), swept-substep bits 8 .. 28; uhc_rollout_record counts int64 [7] */
 
 /* joint / geom type codes (MuJoCo numbering) */
 enum { UHC_JNT_FREE = 0, UHC_JNT_BALL = 1, UHC_JNT_SLIDE = 2, UHC_JNT_HINGE = 3 };
@@ -370,6 +370,28 @@ int32_t uhc_filter_push(void* stream, const double* d_x, int32_t n_rows, int32_t
  * clip == 0: no clipping.  d_t_inc (may be NULL): incremented by one -- the step counter, this being the last launch of a step */
 int32_t uhc_filter_apply(void* stream, const double* d_x, int32_t n_rows, int32_t dim, const double* d_n, const double* d_mean, const double* d_S,
                          int32_t demean, int32_t destd, double clip, double* d_out, int64_t* d_t_inc);
+
+/* ------------------------------------------------------------------ expert frame records of a clip bank, computed on the device
+ * Replaces Humanoid.qpos_fk (uhc/smpllib/torch_smpl_humanoid.py:234-261: Euler angles -> joint quaternions, forward kinematics, the two finite
+ * differences) and the feature half of HumanoidEnv.load_expert (uhc/envs/humanoid_im.py:182-215) for a whole bank in ONE launch: a free function
+ * like uhc_rollout_*, `stream` a hipStream_t (NULL = the default stream).
+ *   n_body           24: UHC_FRAME_STRIDE is a 24-body layout
+ *   h_parent [24]    HOST: parent of every body behind the world body, -1 for the root (body 0); a parent precedes its child
+ *   h_ee_body [5]    HOST: indices 0 .. 23 of SMPL_EE_NAMES among those bodies
+ *   d_body_pos, d_body_ipos [n_models][24][3]: model.body_pos / body_ipos behind the world body
+ *   d_qpos [n_frames][76]: root position, root quaternion wxyz, 23 x 3 Euler angles (z, y, x) in the model's body order; the clips one after another
+ *   d_clip_start int32 [n_clips], ascending from 0; the last clip ends at n_frames (as in uhc_env_set_bank)
+ *   d_clip_model int32 [n_clips] or NULL (= model 0 for every clip): whose offsets a clip's frames are computed with
+ *   d_root_quat_record [n_frames][4] or NULL: written into the record's qpos[3:7] INSTEAD of d_qpos' quaternion; kinematics and velocities keep
+ *                    reading d_qpos (the ball-joint humanoid's second conversion: uhc/envs/humanoid_im.py:193-200)
+ *   dt               frame time of the clips (1 / 30)
+ *   d_frames [n_frames][UHC_FRAME_STRIDE]: out.  Slots 505 .. 511 are written as zeros.
+ * Frame t >= 1 of a clip differences frames (t - 1, t); frame 0 takes frame 1's velocities; no difference reaches across a clip boundary.
+ * A clip of ONE frame gets zero qvel and bangvel (the reference cannot compute such a clip at all).  qvel is clipped to +-10, bangvel is not.
+ * Every argument is checked before the first HIP call; n_frames == 0 succeeds and launches nothing. */
+int32_t uhc_expert_frames(void* stream, int32_t n_body, const int32_t* h_parent, const int32_t* h_ee_body, const double* d_body_pos,
+                          const double* d_body_ipos, int32_t n_models, const double* d_qpos, int64_t n_frames, const int32_t* d_clip_start,
+                          const int32_t* d_clip_model, int32_t n_clips, const double* d_root_quat_record, double dt, double* d_frames);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -20,6 +20,7 @@ SYMBOLS = [
     "uhc_env_create", "uhc_env_free", "uhc_env_obs_dim", "uhc_env_field", "uhc_env_set_bank", "uhc_env_assign",
     "uhc_env_reset", "uhc_env_step", "uhc_env_set_next", "uhc_env_auto_reset", "uhc_env_set_clip_models", "uhc_env_set_end_reward", "uhc_env_set_obj_pose",
     "uhc_rollout_act", "uhc_rollout_record", "uhc_filter_scratch_doubles", "uhc_filter_push", "uhc_filter_apply",
+    "uhc_expert_frames",
 ]
 
 
@@ -85,6 +86,9 @@ def lib():
     L.uhc_filter_scratch_doubles.restype = C.c_int64
     L.uhc_filter_push.argtypes = [P, P, I, I, P, P, P, P, P]
     L.uhc_filter_apply.argtypes = [P, P, I, I, P, P, P, I, I, D, P, P]
+    if hasattr(L, "uhc_expert_frames"):  # (ABI 11)
+        L.uhc_expert_frames.argtypes = [P, I, C.POINTER(I), C.POINTER(I), P, P, I, P, C.c_int64, P, P, I, P, D, P]
+        L.uhc_expert_frames.restype = I
     _lib = L
     return L
 

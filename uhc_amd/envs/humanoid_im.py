@@ -158,9 +158,15 @@ class VecHumanoidEnv:
             raise ValueError(f"the env carries {self.num_obj} objects: every clip needs obj_pose of shape (T, {7 * self.num_obj})")
         return op
 
-    def set_clip_bank(self, clips: dict, clip_model: dict = None):
+    def set_clip_bank(self, clips: dict, clip_model: dict = None, build: str = "host"):
         """clips: {key: sample dict with pose_aa/trans/beta/gender (+ obj_pose when the env carries objects) of the WHOLE clip}.  Builds the
-        HBM bank once.  clip_model: {key: index into [model] + shape_models}: the body shape every episode of that clip runs on."""
+        HBM bank once.  clip_model: {key: index into [model] + shape_models}: the body shape every episode of that clip runs on.
+        build: "host" -- qpos_fk and the packing of the frame records clip by clip on the host, the records uploaded; "device" -- only the
+        AMASS -> qpos conversion on the host, ONE upload of the qpos rows and ONE uhc_expert_frames launch for the whole bank."""
+        if build not in ("host", "device"):
+            raise ValueError(f"set_clip_bank: build must be 'host' or 'device', got {build!r}")
+        if build == "device":
+            return self._set_clip_bank_device(clips, clip_model)
         frames, starts, betas, lens, objs = [], [], [], [], []
         n = 0
         self.clip_keys = list(clips.keys())
@@ -186,10 +192,53 @@ class VecHumanoidEnv:
         self.env.set_obj_pose(torch.from_numpy(np.concatenate(objs)) if self.num_obj else None)
         self.env.set_clip_models(torch.tensor(cm, dtype=torch.int32) if clip_model else None)
 
-    def set_clip_bank_from_loader(self, data_loader, clip_model=None):
+    @staticmethod
+    def _clip_beta_row(c):
+        beta = np.asarray(c["beta"], dtype=np.float64)
+        beta = beta[0] if beta.ndim == 2 else beta
+        beta = np.concatenate([beta, np.zeros(16 - beta.shape[0])]) if beta.shape[0] < 16 else beta[:16]
+        return np.r_[beta, float(np.asarray(c["gender"]).reshape(-1)[0])]
+
+    def _set_clip_bank_device(self, clips, clip_model):
+        """set_clip_bank(build="device"): the host keeps smpl_to_qpose (scipy's Euler branch rules); everything behind it -- Humanoid.qpos_fk and
+        pack_expert_frames -- is uhc_expert_frames on the env's stream, on each clip's own body shape."""
+        self.clip_keys = list(clips.keys())
+        cm = [int(clip_model[k]) if clip_model else 0 for k in self.clip_keys]
+        rows, quats, starts, betas, lens, objs = [], [], [], [], [], []
+        n = 0
+        for k, mi in zip(self.clip_keys, cm):
+            c = clips[k]
+            kin = self.body_models[mi]
+            kw = dict(pose=c["pose_aa"], trans=np.asarray(c["trans"]).squeeze(), model=self.cc_cfg.robot_cfg.get("model", "smpl"),
+                      count_offset=self.cc_cfg.robot_cfg.get("mesh", True))
+            q = np.asarray(smpl_to_qpose(mj_model=kin, **kw), dtype=np.float64)
+            rows.append(q)
+            if self.use_quat:  # the record's root quaternion comes out of the second conversion (expert_features)
+                quats.append(np.asarray(smpl_to_qpose(mj_model=kin, use_quat=True, **kw), dtype=np.float64)[:, 3:7])
+            if self.num_obj:
+                objs.append(self._clip_obj_pose(c, q.shape[0]))
+            starts.append(n)
+            lens.append(q.shape[0])
+            n += q.shape[0]
+            betas.append(self._clip_beta_row(c))
+        self._clip_index = {k: i for i, k in enumerate(self.clip_keys)}
+        self._clip_len = np.array(lens)
+        for i, m in enumerate(self.body_models):  # (the offset tables of every body shape travel, whether or not a clip of this bank names it)
+            if i not in self._humanoids:
+                self._humanoids[i] = Humanoid(model=m)
+        hums = [self._humanoids[i] for i in range(len(self.body_models))]
+        with torch.cuda.device(self.device):
+            frames = S.expert_frames_device(torch.from_numpy(np.concatenate(rows)), starts, hums,
+                                            clip_model=cm if clip_model else None,
+                                            root_quat_record=torch.from_numpy(np.concatenate(quats)) if self.use_quat else None, device=self.device)
+        self.env.set_bank(frames, torch.tensor(starts, dtype=torch.int32), torch.from_numpy(np.stack(betas)))
+        self.env.set_obj_pose(torch.from_numpy(np.concatenate(objs)) if self.num_obj else None)
+        self.env.set_clip_models(torch.tensor(cm, dtype=torch.int32) if clip_model else None)
+
+    def set_clip_bank_from_loader(self, data_loader, clip_model=None, build="host"):
         clips = {k: dict(pose_aa=data_loader.data["pose_aa"][k], trans=data_loader.data["trans"][k], beta=data_loader.data["beta"][k],
                          gender=data_loader.data["gender"][k], obj_pose=data_loader.data.get("obj_pose", {}).get(k)) for k in data_loader.data_keys}
-        self.set_clip_bank(clips, clip_model=clip_model)
+        self.set_clip_bank(clips, clip_model=clip_model, build=build)
 
     def _window_len(self, fr_start, fr_end):
         n = np.asarray(fr_end) - np.asarray(fr_start)
@@ -372,7 +421,7 @@ class HumanoidEnv(MujocoEnv):
         self.expert = dict(expert_data)
         self.expert["meta"] = {"cyclic": False, "seq_name": expert_data["seq_name"]}
         self.expert.update(self.vec.expert_features(expert_data))
-        self.vec.set_clip_bank({expert_data["seq_name"]: expert_data})
+        self.vec.set_clip_bank({expert_data["seq_name"]: expert_data}, build=getattr(self.cc_cfg, "bank_build", "host"))  # (self.expert above stays the host's: the getters read it)
         self.vec.assign([0], [expert_data["seq_name"]], [0], [self.expert["len"]])
 
     def reset_model(self):  # (MujocoEnv.reset calls it: mujoco_env.py:95-104)

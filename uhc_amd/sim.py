@@ -220,6 +220,60 @@ def expert_pose_of_frames(frames, ball: bool):
     return qpos, frames[:, v0:v0 + vn]
 
 
+def expert_frames_device(qpos, clip_start, humanoids, clip_model=None, root_quat_record=None, dt: float = 1 / 30, device=None) -> torch.Tensor:
+    """The clip bank's frame records computed on the device (uhc_expert_frames): what `pack_expert_frames(Humanoid.qpos_fk(clip))`, clip by
+    clip, gives on the host, from ONE upload of the thin qpos rows and ONE launch on torch's current stream.
+      qpos (n_frames, 76): the clips' hinge qpos one after another (numpy or torch, host or device); clip_start: first row of every clip;
+      humanoids: one `Humanoid` (or a list of them, same tree) per body shape -- their offset tables are uploaded once --, clip_model: which of
+      them each clip is computed with (None: the first for every clip); root_quat_record (n_frames, 4): written into the records' qpos[3:7]
+      instead of qpos' own quaternion, which kinematics and velocities keep reading.
+    Returns the (n_frames, FRAME_STRIDE) float64 device tensor `EnvBatch.set_bank` takes without a copy.  A clip of one frame gets zero qvel / bangvel."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("uhc_amd.sim.expert_frames_device needs an MI355X (torch.cuda unavailable); there is no CPU fallback")
+    hs = list(humanoids) if isinstance(humanoids, (list, tuple)) else [humanoids]
+    if device is None:
+        device = qpos.device if isinstance(qpos, torch.Tensor) and qpos.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    parents = np.ascontiguousarray(hs[0]._parents, dtype=np.int32)
+    ee = np.ascontiguousarray(hs[0]._ee_idx, dtype=np.int32)
+    for h in hs[1:]:
+        if not np.array_equal(np.asarray(h._parents), parents) or list(h._ee_idx) != list(ee):
+            raise ValueError("expert_frames_device: every body shape must share the first one's tree")
+    if ee.shape != (5,):
+        raise ValueError("expert_frames_device: five end effectors (SMPL_EE_NAMES) are what the frame record holds")
+    cs = np.asarray(clip_start.cpu() if isinstance(clip_start, torch.Tensor) else clip_start, dtype=np.int64).reshape(-1)
+    qpos = torch.as_tensor(qpos)
+    n_frames = int(qpos.shape[0])
+    if qpos.ndim != 2 or qpos.shape[1] != 76:
+        raise ValueError(f"expert_frames_device: qpos must be (n_frames, 76), got {tuple(qpos.shape)}")
+    if cs.size == 0 or cs[0] != 0 or np.any(np.diff(cs) <= 0) or (n_frames and cs[-1] >= n_frames):
+        raise ValueError("expert_frames_device: clip_start must ascend strictly from 0 and stay below n_frames")
+    cm = None
+    if clip_model is not None:
+        cm = np.asarray(clip_model.cpu() if isinstance(clip_model, torch.Tensor) else clip_model, dtype=np.int64).reshape(-1)
+        if cm.shape != cs.shape or cm.min() < 0 or cm.max() >= len(hs):
+            raise ValueError(f"expert_frames_device: clip_model must name one of the {len(hs)} body shapes for each of the {cs.size} clips")
+    if n_frames == 0:
+        return torch.empty((0, FRAME_STRIDE), dtype=torch.float64, device=device)
+    with torch.cuda.device(device):  # (the temporaries below are freed in stream order: the launch is on torch's current stream)
+        off = torch.stack([h._offsets for h in hs]).to(device, torch.float64).contiguous()
+        ioff = torch.stack([h._i_offsets for h in hs]).to(device, torch.float64).contiguous()
+        q = qpos.to(device, torch.float64).contiguous()
+        d_cs = torch.from_numpy(cs.astype(np.int32)).to(device)
+        d_cm = None if cm is None else torch.from_numpy(cm.astype(np.int32)).to(device)
+        rq = None
+        if root_quat_record is not None:
+            rq = torch.as_tensor(root_quat_record).to(device, torch.float64).contiguous()
+            if rq.shape != (n_frames, 4):
+                raise ValueError(f"expert_frames_device: root_quat_record must be ({n_frames}, 4), got {tuple(rq.shape)}")
+        out = torch.empty((n_frames, FRAME_STRIDE), dtype=torch.float64, device=device)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        check(lib().uhc_expert_frames(C.c_void_p(torch.cuda.current_stream(device).cuda_stream), int(off.shape[1]),
+                                      parents.ctypes.data_as(C.POINTER(C.c_int32)), ee.ctypes.data_as(C.POINTER(C.c_int32)), ptr(off), ptr(ioff), len(hs),
+                                      ptr(q), n_frames, ptr(d_cs), ptr(d_cm), int(cs.size), ptr(rq), float(dt), ptr(out)))
+    return out
+
+
 class EnvBatch:
     """Device env layer (uhc_env_* of the C-ABI) on top of a SimBatch."""
 

@@ -48,6 +48,12 @@ class Humanoid:
             com.append(quat_mul_vec_batch(q, ioff[i].expand_as(root_positions)) + p)
         return torch.stack(pos, 1), torch.stack(com, 1), torch.stack(rot, 1)
 
+    def frames_device(self, qpos, clip_start=(0,), root_quat_record=None, device=None):
+        """The frame records of the clip bank for clips of THIS body, computed on the device: uhc_amd.sim.expert_frames_device (several body
+        shapes in one launch: call that with the list of Humanoids and the clips' model indices)."""
+        from ..sim import expert_frames_device
+        return expert_frames_device(qpos, clip_start, [self], root_quat_record=root_quat_record, device=device)
+
     def qpos_fk(self, qpos, to_numpy=True):
         """qpos (T,76) -> the expert feature dict of torch_smpl_humanoid.py:234-261."""
         qpos = qpos.clone()

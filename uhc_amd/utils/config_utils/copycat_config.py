@@ -93,6 +93,11 @@ class Config(Base_Config):
         self.contact_solver = g("contact_solver", 1)
         self.pgs_iterations = g("pgs_iterations", 300)
         self.n_env = g("n_env", 1024)
+        # where the clip bank's frame records are computed (VecHumanoidEnv.set_clip_bank(build=)): "host" -- Humanoid.qpos_fk clip by clip, the records
+        # uploaded --, "device" -- the qpos rows uploaded, one uhc_expert_frames launch for the whole bank
+        self.bank_build = g("bank_build", "host")
+        if self.bank_build not in ("host", "device"):
+            raise ValueError(f"bank_build: 'host' or 'device', got {self.bank_build!r}")
         self.ppo_dtype = g("ppo_dtype", "float64")
         # data-parallel gradient exchange: the dtype on the wire.  float32 (default): SURVEY 8e's 32 MB per optimisation epoch; the local
         # gradient means travel scaled by the rank's sample count and are divided by the global count in the parameters' own float64, so the
