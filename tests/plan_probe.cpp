@@ -77,11 +77,32 @@ static int run_plan(const UhcModelDesc* md, int n_env, const UhcCtrlDesc* ctrl, 
     return 0;
 }
 // in: est2, est3, est4, est2_then, handed2, n_env, n_cu, lds_bytes_fast, large_first, last_tier, queues_off, q2_div, q2_wait_min, q2_max, q3_max, q4_max, UHC_DEBUG word
-static void run_sticky(const int* in, int* out) {
-    const StickyInputs si{in[0], in[1], in[2], in[3], in[4], in[5], in[6], (size_t)in[7], in[8] != 0, in[9], in[10] != 0, in[11], in[12], in[13], in[14], in[15], (in[16] & 2048) != 0};
-    const StickySizes s = plan_sticky_step(si);
+static void put_sticky(const StickySizes& s, int* out) {
     const int o[10] = {s.queues, s.waiting, s.q3, s.q4, s.launch4, s.grid2, s.grid3, s.grid4, s.n_wait, s.sticky_mask};
     memcpy(out, o, sizeof o);
+}
+// (the list kernel's decision and the sizes from one queues_off: a step in which the back-off does not flip)
+static StickyInputs sticky_inputs(const int* in) {
+    return StickyInputs{in[0], in[1], in[2], in[3], in[4], in[5], in[6], (size_t)in[7], in[8] != 0, in[9], in[10] != 0, in[11], in[12], in[13], in[14], in[15], (in[16] & 2048) != 0};
+}
+static void run_sticky(const int* in, int* out) { put_sticky(plan_sticky_step(sticky_inputs(in)), out); }
+// in: the 17 words above, n_substeps, fast_chunk, the queues_off the step BEGAN with (what the list kernel's decision saw; in[10] is the one after the back-off
+// update).  out: the 10 words of run_sticky; the fast tier's chunk, n_chunks, grid, prod_total; the number of launches;
+// per launch WIRING_WORDS words in the order of StepLaunch's declaration
+#define WIRING_WORDS 20
+static void run_wiring(const int* in, int* out) {
+    StickyInputs si = sticky_inputs(in);
+    si.n_substeps = in[17]; si.fast_chunk = in[18];
+    const StickySizes s = plan_sticky_step(si, sticky_launch4(si.last_tier, si.est4, si.est2_then, in[19] != 0));
+    const StepWiring w = sticky_wiring(s, si.large_first);
+    put_sticky(s, out);
+    out[10] = s.fast.chunk; out[11] = s.fast.n_chunks; out[12] = s.fast.grid; out[13] = s.fast.prod_total; out[14] = w.n;
+    for (int k = 0; k < 4; k++) {
+        const StepLaunch& l = w.launch[k];
+        const int o[WIRING_WORDS] = {l.tier, l.stream, l.list, l.count, l.cursor, l.grid, l.n_wait, l.spares, l.started, l.prod_fin, l.prod_total, l.fin, l.next_list, l.next_count,
+                                     l.gate_started, l.gate_want, l.gate_waited, l.tier_want, l.chunk, l.use_order};
+        memcpy(out + 15 + WIRING_WORDS * k, o, sizeof o);
+    }
 }
 // C interface of the probe (tests/test_batch_plan_cpu.py): one plan at a time, kept until the next call
 static Words g_words;
@@ -133,3 +154,4 @@ extern "C" __attribute__((visibility("default"))) long long uhc_plan_probe_table
     return -1;
 }
 extern "C" __attribute__((visibility("default"))) void uhc_plan_probe_sticky(const int* in17, int* out10) { run_sticky(in17, out10); }
+extern "C" __attribute__((visibility("default"))) void uhc_plan_probe_wiring(const int* in20, int* out95) { run_wiring(in20, out95); }

@@ -1,7 +1,8 @@
 """The batch plan on the CPU: uhc_amd/csrc/uhc_plan.cpp (pure host C++, no HIP runtime) compiled with the host compiler beside a thin probe
 (tests/plan_probe.cpp) and asked for the plan of every model class the GPU tests and bench.py run.
 
-a. Invariants of the LDS layouts, the schedules, the marks, the guard table and the sticky-step sizes: what the kernels rely on and nothing else states.
+a. Invariants of the LDS layouts, the schedules, the marks, the guard table, the sticky-step sizes and the step's table of launches: what the kernels rely on and
+   nothing else states.
 b. Equality with tests/batch_plan_recording.json: the plan words and table hashes the unrefactored uhc_batch_create gave for the same inputs (recorded once, at the
    commit before the planner was split out, from that commit's uhc_capi.cpp compiled host-only with stand-ins for the hip* calls), and the outputs of the sticky
    launch arithmetic lifted from its launch()."""
@@ -10,6 +11,7 @@ import dataclasses
 import itertools
 import json
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -112,8 +114,29 @@ class Probe:
         self.L.uhc_plan_probe_sticky(a, o)
         return [int(x) for x in o]
 
+    def wiring(self, inp, n_substeps, fast_chunk, off_at_head=None):
+        """off_at_head: the queues_off the step began with, which the list kernel's launch4 was decided from (default: inp's, the step's back-off did not flip)
+        -> (sticky sizes {name: int}, the fast tier's chunks {name: int}, the step's launches [{field: int or None}] in launch order)"""
+        nw = len(WIRING_FIELDS)
+        a, o = (C.c_int * 20)(*inp, n_substeps, fast_chunk, inp[10] if off_at_head is None else off_at_head), (C.c_int * (15 + 4 * nw))()
+        self.L.uhc_plan_probe_wiring(a, o)
+        o = [int(x) for x in o]
+        launches = [dict(zip(WIRING_FIELDS, o[15 + nw * k:15 + nw * (k + 1)])) for k in range(o[14])]
+        for l in launches:
+            for f in WIRING_SLOTS:
+                l[f] = None if l[f] == -1 else l[f]  # UHC_NONE
+        return dict(zip(STICKY_OUT, o[:10])), dict(zip(("chunk", "n_chunks", "grid", "prod_total"), o[10:14])), launches
+
 
 STICKY_OUT = ("queues", "waiting", "q3", "q4", "launch4", "grid2", "grid3", "grid4", "n_wait", "sticky_mask")
+# StepLaunch (uhc_plan.h) in the order of its declaration; the fields that hold a slot of the batch's lists / counts / cursors / fin, or none
+WIRING_FIELDS = ("tier", "stream", "list", "count", "cursor", "grid", "n_wait", "spares", "started", "prod_fin", "prod_total", "fin", "next_list", "next_count",
+                 "gate_started", "gate_want", "gate_waited", "tier_want", "chunk", "use_order")
+WIRING_SLOTS = ("list", "count", "cursor", "spares", "started", "prod_fin", "fin", "next_list", "next_count", "gate_started", "gate_waited")
+SLOT = {k: int(v) for k, v in re.findall(r"\b(UHC_[A-Z0-9_]+) = (\d+)", open(os.path.join(CSRC, "uhc_device.h")).read())}  # the enumerators the list kernel indexes by
+N_WORDS, N_LISTS = int(re.search(r"#define UHC_N_WORDS (\d+)", open(os.path.join(CSRC, "uhc_device.h")).read()).group(1)), SLOT["UHC_N_LISTS"]  # ints allocated for counts / cursors / fin; env queues
+# what uhc_tier_lists_kernel fills for each tier's consumers: (list, count, cursor)
+QUEUE_OF_TIER = {2: ("UHC_LIST_GEN", "UHC_CNT_GEN", "UHC_CUR_GEN"), 3: ("UHC_LIST_BIG", "UHC_CNT_BIG", "UHC_CUR_BIG"), 4: ("UHC_LIST_T4", "UHC_CNT_T4", "UHC_CUR_T4")}
 
 
 @pytest.fixture(scope="module")
@@ -259,6 +282,94 @@ def test_sticky_step_invariants(probe):
         assert o["grid2"] <= n_env, inp
         assert o["grid4"] <= q4_max, inp
         assert o["sticky_mask"] == 4 * o["queues"] + 8 * o["q3"] + 16 * o["launch4"]
+
+
+def wiring_cases():
+    """(inputs, queues_off at the head of the step): the sticky grid; the same with three and two tiers (no tier 4; no large tier either); and the step in which the
+    back-off flips -- launch4 decided while the queues were still on, the sizes planned with them off."""
+    grid = sticky_inputs()
+    cases = [(inp, inp[10]) for inp in grid]
+    for last_tier in (3, 2):
+        cases += [(inp[:9] + [last_tier] + inp[10:], inp[10]) for inp in grid]
+    return cases + [(inp, 0) for inp in grid if inp[10] == 1]
+
+
+@pytest.mark.parametrize("n_substeps,fast_chunk", [(0, 0), (15, 0), (15, 3), (15, 5), (15, 15)])
+def test_sticky_wiring_invariants(probe, n_substeps, fast_chunk):
+    """The step's table of launches (sticky_wiring): every invariant between a queue's producers and its consumers, whatever the sizes, and the queue each tier's
+    consumers read is the one the list kernel fills for that tier."""
+    for inp, off_at_head in wiring_cases():
+        z, fast, launches = probe.wiring(inp, n_substeps, fast_chunk, off_at_head)
+        n_env, large_first, last_tier = inp[5], inp[8], inp[9]
+        by_tier = {l["tier"]: l for l in launches}
+        assert len(by_tier) == len(launches), inp
+        consumers = [l for l in launches if l["list"] is not None]
+        for l in consumers:
+            assert (l["list"], l["count"], l["cursor"]) == tuple(SLOT[k] for k in QUEUE_OF_TIER[l["tier"]]), inp
+        assert (3 in by_tier) == bool(z["queues"] and last_tier >= 3) and (last_tier == 4 or 4 not in by_tier), inp
+        assert z["launch4"] == (last_tier == 4 and inp[2] > 0 and inp[3] > 0 and not off_at_head), inp  # sticky_launch4 of what the step began with
+        # which launches the step has, and the mask the kernels filter by
+        assert set(by_tier) == {1} | ({2} if z["queues"] else set()) | ({3} if z["q3"] else set()) | ({4} if z["q4"] else set()), inp
+        assert z["sticky_mask"] == 4 * (2 in by_tier) + 8 * (3 in by_tier) + 16 * z["launch4"], inp
+        assert (4 in by_tier) == bool(z["launch4"] and 3 in by_tier), inp
+        # the order: tier 4 first, large before general exactly when large_first, the fast tier last
+        want = [t for t in ([4, 3, 2] if large_first else [4, 2, 3]) if t in by_tier] + [1]
+        assert [l["tier"] for l in launches] == want, inp
+        assert [l["stream"] for l in launches] == [{1: 0, 2: 1, 3: 2, 4: 3}[t] for t in want], inp  # the batch's stream; a side stream per tier
+        # the fast tier's launch
+        f = by_tier[1]
+        assert f["list"] is None and f["count"] is None and f["cursor"] is None and f["tier_want"] == 1 and f["use_order"] == 1, inp
+        assert f["chunk"] == fast["chunk"] and f["grid"] == fast["grid"] == fast["n_chunks"] * n_env, inp
+        assert (f["chunk"] == 0) == (fast["n_chunks"] == 1), inp
+        assert (f["fin"] is not None) == (f["next_list"] is not None) == (f["next_count"] is not None) == bool(z["waiting"]), inp
+        for l in consumers:
+            assert l["list"] is not None and l["count"] is not None and l["cursor"] is not None and l["grid"] > 0, inp
+            assert l["tier_want"] == 0 and l["chunk"] == 0 and l["use_order"] == 0, inp
+            assert l["grid"] == {2: z["grid2"], 3: z["grid3"], 4: z["grid4"]}[l["tier"]], inp
+        # producers: a consumer waits for the exits of a launch of this step, all of them
+        for l in consumers:
+            if l["prod_fin"] is None:
+                assert l["prod_total"] == 0, inp
+                continue
+            prod = [p for p in launches if p["fin"] == l["prod_fin"]]
+            assert len(prod) == 1 and prod[0] is not l, inp
+            assert l["prod_total"] == prod[0]["grid"], inp
+        # hand-ons: into the queue of a consumer launch of this step, and only from the tier directly below it
+        for l in launches:
+            assert (l["next_list"] is None) == (l["next_count"] is None), inp
+            if l["next_list"] is not None:
+                into = [c for c in consumers if (c["list"], c["count"]) == (l["next_list"], l["next_count"])]
+                assert len(into) == 1 and into[0]["tier"] == l["tier"] + 1, inp
+                assert into[0]["prod_fin"] == l["fin"] and l["fin"] is not None, inp  # whoever appends to a queue is waited for by its consumers
+        # gates: for a consumer launch of this step to be resident, all of it
+        for l in launches:
+            if l["gate_started"] is None:
+                assert l["gate_want"] == 0 and l["gate_waited"] is None, inp
+                continue
+            behind = [c for c in consumers if c["started"] == l["gate_started"]]
+            assert len(behind) == 1 and l["gate_want"] == behind[0]["grid"], inp
+            assert launches.index(behind[0]) < launches.index(l), inp
+        if 2 in by_tier:
+            assert (by_tier[2]["gate_started"] is not None) == bool(3 in by_tier and large_first), inp
+        assert (f["gate_started"] is not None) == bool(z["waiting"]), inp
+        assert all(by_tier[t]["gate_started"] is None for t in (3, 4) if t in by_tier), inp
+        # no slot is shared, none lies beyond the allocation
+        for field, room in (("list", N_LISTS), ("count", N_WORDS), ("cursor", N_WORDS)):
+            used = [l[field] for l in consumers] + ([l["gate_waited"] for l in launches if l["gate_waited"] is not None] if field == "count" else [])
+            assert len(set(used)) == len(used) and all(0 <= u < room for u in used), (field, inp)
+        fins = [l[k] for l in launches for k in ("fin", "started", "spares") if l[k] is not None]
+        assert len(set(fins)) == len(fins) and all(0 <= u < N_WORDS for u in fins), inp
+        for l in launches:
+            for k in ("prod_fin", "gate_started"):
+                assert l[k] is None or 0 <= l[k] < N_WORDS, inp
+            assert l["next_list"] is None or (0 <= l["next_list"] < N_LISTS and 0 <= l["next_count"] < N_WORDS), inp
+        # who waits on an empty queue: the general tier's consumers share a seat counter, every other consumer waits
+        for l in consumers:
+            if l["tier"] == 2:
+                assert l["spares"] is not None and l["n_wait"] == z["n_wait"], inp
+            else:
+                assert l["spares"] is None and l["n_wait"] == l["grid"], inp
+        assert f["spares"] is None and f["n_wait"] == 0 and f["started"] is None and f["prod_fin"] is None, inp
 
 
 # ---------------------------------------------------------------------------------------------------------------- b. equality with the recording

@@ -49,20 +49,20 @@ extern "C" hipError_t uhc_launch_set_state(const DevState* s, int nq, int nv, in
 }
 
 // sticky tiers, head of a control step: snapshot of the tier table + the queues of the general / large tier, which start with the active
-// envs that begin the step there (lists[0 .. n_env) = tier 2, lists[n_env .. 2 n_env) = tier 3; counts[2], counts[3]; free slots = -1),
-// the cursors the persistent launches share and the producers' exit counters (fin[1]: fast tier's workgroups, fin[2]: general tier's)
+// envs that begin the step there (lists UHC_LIST_GEN, UHC_LIST_BIG of n_env slots each, free slots = -1; counts UHC_CNT_GEN, UHC_CNT_BIG),
+// the cursors the persistent launches share and the counters their workgroups bump (UhcFin).  The words' names: uhc_device.h
 #define UHC_ORDER_BUCKETS 9
-// (tier 4, `launch4` != 0: tier 4's queue consumers run this step; the envs whose last step ended in tier 4 (UHC_DEBUG bit 12 only) head their queue -- lists[2 n_env ..),
-//  counts[6] -- and are flagged pend3 = 2, "straight to tier 4"; with launch4 == 0 they are the large tier's like any tier-3 env and the snapshot says 3)
+// (tier 4, `launch4` != 0: tier 4's queue consumers run this step; the envs whose last step ended in tier 4 (UHC_DEBUG bit 12 only) head their queue -- list UHC_LIST_T4,
+//  count UHC_CNT_T4 -- and are flagged pend3 = 2, "straight to tier 4"; with launch4 == 0 they are the large tier's like any tier-3 env and the snapshot says 3)
 __global__ void uhc_tier_lists_kernel(const int* tier, const int* d_active, int n_env, int* tier_now, int* lists, int* counts, int* cursors, int* fin,
                                       const int* cost, const int* fresh, int* order, int launch4, int* pend3) {
     __shared__ int nb[UHC_ORDER_BUCKETS + 1];
-    if (threadIdx.x < 4) counts[threadIdx.x] = 0;
-    if (threadIdx.x < 8) cursors[threadIdx.x] = 0;
-    if (threadIdx.x >= 6 && threadIdx.x < 8) counts[threadIdx.x] = 0;
-    if (threadIdx.x < 8) fin[threadIdx.x] = 0;  // exit counters of the fast / general tier's workgroups [1], [2]; spare seats taken [0]; consumers resident [3], [4]
+    if (threadIdx.x < UHC_CNT_GEN_HEAD) counts[threadIdx.x] = 0;  // (the two head-of-step counts are written below)
+    if (threadIdx.x < UHC_N_WORDS) cursors[threadIdx.x] = 0;
+    if (threadIdx.x >= UHC_CNT_T4 && threadIdx.x < UHC_N_WORDS) counts[threadIdx.x] = 0;
+    if (threadIdx.x < UHC_N_WORDS) fin[threadIdx.x] = 0;
     if (threadIdx.x <= UHC_ORDER_BUCKETS) nb[threadIdx.x] = 0;
-    for (int i = threadIdx.x; i < 3 * n_env; i += blockDim.x) lists[i] = -1;
+    for (int i = threadIdx.x; i < UHC_N_LISTS * n_env; i += blockDim.x) lists[i] = -1;
     __syncthreads();
     // the fast tier's launch order: its envs from the costliest bucket down (cost = how close the env's last step came to the tier's
     // capacity, which is also what its step time grows with), then the envs that are not this launch's.  The launch does not fit the chip
@@ -83,16 +83,16 @@ __global__ void uhc_tier_lists_kernel(const int* tier, const int* d_active, int 
         const bool on = !d_active || d_active[env];
         if (t == 4 && fresh[env]) t = 2;  // (a restarted env has no history: its reset pose is the general tier's to look at, not a whole CU's)
         if (t == 4) {
-            if (on) atomicAdd(&counts[7], 1);  // (counts[7]: the step's tier-4 envs -- these and every hand-on to tier 4 (KernelArgs::cnt4); the host sizes the NEXT steps' tier-4 consumers by it)
-            if (launch4 && on) { lists[2 * n_env + atomicAdd(&counts[6], 1)] = env; pend3[env] = 2; }
+            if (on) atomicAdd(&counts[UHC_CNT_T4_STEPS], 1);  // (the step's tier-4 envs: these and every hand-on to tier 4, KernelArgs::cnt4)
+            if (launch4 && on) { lists[UHC_LIST_T4 * n_env + atomicAdd(&counts[UHC_CNT_T4], 1)] = env; pend3[env] = 2; }
             else if (!launch4) t = 3;
         }
         tier_now[env] = t;
-        if ((t == 2 || t == 3) && on) lists[(t - 2) * n_env + atomicAdd(&counts[t], 1)] = env;
+        if ((t == 2 || t == 3) && on) lists[(UHC_LIST_GEN + t - 2) * n_env + atomicAdd(&counts[UHC_CNT_GEN + t - 2], 1)] = env;
         if (order) atomicAdd(&nb[bucket(env)], 1);
     }
     __syncthreads();
-    if (threadIdx.x < 2) counts[4 + threadIdx.x] = counts[2 + threadIdx.x];  // the queues as the step begins (the host compares with how they end)
+    if (threadIdx.x < 2) counts[UHC_CNT_GEN_HEAD + threadIdx.x] = counts[UHC_CNT_GEN + threadIdx.x];  // the queues as the step begins (the host compares with how they end)
     if (!order) return;
     if (threadIdx.x == 0) {
         int run = 0;

@@ -224,12 +224,14 @@ static int alloc_state(UhcBatch* b, const UhcModel* const* models, const int32_t
     TRY(dalloc(b, E * nq, &S.qpos)); TRY(dalloc(b, E * nv, &S.qvel)); TRY(dalloc(b, E * nv, &S.qacc)); TRY(dalloc(b, E * nv, &S.qacc_ws));
     TRY(dalloc(b, E * 3 * nb, &S.xpos)); TRY(dalloc(b, E * 4 * nb, &S.xquat)); TRY(dalloc(b, E * 3 * nb, &S.xipos));
     TRY(dalloc(b, 4, &S.path_stats));
-    TRY(dalloc(b, E * A.t.nM, &S.qM)); TRY(dalloc(b, 6 * E + 1, &S.redo)); S.pend2 = S.redo + E; S.pend3 = S.redo + 2 * E; S.resume = S.redo + 3 * E; S.why = S.redo + 4 * E; TRY(dalloc(b, 2, &S.q_abort));
-    A.chunk_done = S.redo + 5 * E; A.ticket = S.redo + 6 * E; TRY(dalloc(b, E * UHC_CHUNK_REC, &A.chunk_rec));  // (the chunked fast tier: progress words and ticket counter are reset with redo .. why)
+    TRY(dalloc(b, E * A.t.nM, &S.qM)); TRY(dalloc(b, 2, &S.q_abort));
+    const StepWords W = step_words(E);  // (one allocation: the chunked fast tier's progress words and ticket counter are reset with redo .. why)
+    TRY(dalloc(b, W.total, &S.redo)); S.pend2 = S.redo + W.pend2; S.pend3 = S.redo + W.pend3; S.resume = S.redo + W.resume; S.why = S.redo + W.why;
+    A.chunk_done = S.redo + W.chunk_done; A.ticket = S.redo + W.ticket; TRY(dalloc(b, E * UHC_CHUNK_REC, &A.chunk_rec));
     TRY(dalloc(b, E, &S.tier)); TRY(dalloc(b, E, &b->tier_now)); S.tier_now = b->tier_now; TRY(dalloc(b, E, &S.cost));
     if (!(A.dbg & 8)) TRY(dalloc(b, E, &b->d_order));  // (UHC_DEBUG bit 3: the fast tier launches in env order)
-    TRY(dalloc(b, 3 * E, &b->d_lists)); TRY(dalloc(b, 8, &b->d_counts)); TRY(dalloc(b, 8, &b->d_cursors)); TRY(dalloc(b, 8, &b->d_fin));
-    { std::vector<int> one(E, 1); HIP_OK(hipMemcpy(S.tier, one.data(), E * sizeof(int), hipMemcpyHostToDevice)); } TRY(dalloc(b, E, &S.fresh)); TRY(dalloc(b, E * 40, &S.prof)); TRY(dalloc(b, E * nv, &S.bias)); TRY(dalloc(b, E * nu, &S.ctrl));
+    TRY(dalloc(b, UHC_N_LISTS * E, &b->d_lists)); TRY(dalloc(b, UHC_N_WORDS, &b->d_counts)); TRY(dalloc(b, UHC_N_WORDS, &b->d_cursors)); TRY(dalloc(b, UHC_N_WORDS, &b->d_fin));
+    { std::vector<int> one(E, 1); HIP_OK(hipMemcpy(S.tier, one.data(), E * sizeof(int), hipMemcpyHostToDevice)); } TRY(dalloc(b, E, &S.fresh)); TRY(dalloc(b, E * UHC_NPROF, &S.prof)); TRY(dalloc(b, E * nv, &S.bias)); TRY(dalloc(b, E * nu, &S.ctrl));
     TRY(dalloc(b, E * nv, &S.applied));
     if (A.c.rfc_mode == 2) { TRY(dalloc(b, E * 6 * nv, &S.cdof)); TRY(dalloc(b, E * 3 * nb, &S.rootcom)); }
     TRY(dalloc(b, E, &S.ncon)); TRY(dalloc(b, E, &S.nefc)); TRY(dalloc(b, E, &S.fail)); TRY(dalloc(b, E, &S.solver_iter));
@@ -246,10 +248,10 @@ static int alloc_state(UhcBatch* b, const UhcModel* const* models, const int32_t
         HIP_OK(hipMemcpy(S.qpos, q0.data(), q0.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     const int64_t n = (int64_t)E;
-    const UhcBatch::Field fields[21] = {{S.qpos, n * nq}, {S.qvel, n * nv}, {S.xpos, n * 3 * nb}, {S.xquat, n * 4 * nb}, {S.xipos, n * 3 * nb}, {S.qM, n * A.t.nM}, {S.bias, n * nv},
+    const UhcBatch::Field fields[UHC_F_COST + 1] = {{S.qpos, n * nq}, {S.qvel, n * nv}, {S.xpos, n * 3 * nb}, {S.xquat, n * 4 * nb}, {S.xipos, n * 3 * nb}, {S.qM, n * A.t.nM}, {S.bias, n * nv},
                                         {S.qacc, n * nv}, {S.ctrl, n * nu}, {S.ncon, n}, {S.nefc, n}, {S.fail, n}, {S.solver_iter, n}, {S.applied, n * nv}, {S.overflow, n},
-                                        {S.prof, n * 40}, {S.redo, n}, {S.tier, n}, {S.why, n}, {S.qacc_ws, n * nv}, {S.cost, n}};
-    std::copy(fields, fields + 21, b->field);
+                                        {S.prof, n * UHC_NPROF}, {S.redo, n}, {S.tier, n}, {S.why, n}, {S.qacc_ws, n * nv}, {S.cost, n}};
+    std::copy(fields, fields + UHC_F_COST + 1, b->field);
     return 0;
 }
 
@@ -279,7 +281,7 @@ extern "C" int32_t uhc_batch_create(const UhcModel* const* models, int32_t n_mod
     b->lds_bytes = P.lds_bytes; b->lds_bytes_fast = P.lds_bytes_fast; b->lds_bytes_big = P.lds_bytes_big;
     b->use_fast = P.use_fast;
     b->hbm_guard = knobs.guard != 0;
-    b->q2_div = knobs.q2_div; b->q2_wait_min = knobs.q2_wait_min; b->q2_max = knobs.q2_max; b->q3_max = knobs.q3_max; b->q4_max = knobs.q4_max;
+    b->caps = knobs;
     b->fast_chunk = (P.A.dbg & 4) ? 0x7fff : knobs.fast_chunk;  // (UHC_DEBUG bit 2 restarts a handed-on env's step from substep 0: only the whole-step launch can)
     TRY(upload_plan(b, P, models[0]->d, ctrl, h_env_model));
     HIP_OK(uhc_set_lds_limit(b->lds_bytes, b->lds_bytes_fast, b->lds_bytes_big));
@@ -366,8 +368,8 @@ extern "C" int32_t uhc_batch_set_kernel_path(UhcBatch* b, int32_t mode) {
         HIP_OK(hipStreamCreateWithPriority(&b->side_stream3, hipStreamNonBlocking, (least != greatest && least != 0) ? least : greatest));
         b->large_first = least != greatest && least != 0;
         { hipDeviceProp_t pr; HIP_OK(hipGetDeviceProperties(&pr, b->device)); b->n_cu = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256; }
-        HIP_OK(hipHostMalloc((void**)&b->h_counts, sizeof(int) * 8 * 8, hipHostMallocDefault));
-        memset(b->h_counts, 0, sizeof(int) * 8 * 8);
+        HIP_OK(hipHostMalloc((void**)&b->h_counts, sizeof(int) * 8 * UHC_N_WORDS, hipHostMallocDefault));
+        memset(b->h_counts, 0, sizeof(int) * 8 * UHC_N_WORDS);
         for (int k = 0; k < 8; k++) HIP_OK(hipEventCreateWithFlags(&b->cnt_ev[k], hipEventDisableTiming));
         HIP_OK(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
         HIP_OK(hipEventCreateWithFlags(&b->ev_side1, hipEventDisableTiming));
@@ -385,144 +387,143 @@ extern "C" int32_t uhc_batch_set_solver(UhcBatch* b, int32_t solver, int32_t ite
     return 0;
 }
 extern "C" int32_t uhc_batch_field(UhcBatch* b, int32_t f, void** p, int64_t* n) {
-    if (!b || f < 0 || f > 20 || !b->field[f].ptr) return fail("uhc_batch_field: unknown field %d", f);
+    if (!b || f < 0 || f > UHC_F_COST || !b->field[f].ptr) return fail("uhc_batch_field: unknown field %d", f);
     if (p) *p = b->field[f].ptr;
     if (n) *n = b->field[f].count;
     return 0;
 }
+typedef std::pair<hipEvent_t, hipEvent_t> EvPair;
+// a launch on the batch's stream between two HIP events when the step is timed (ev != null): "the kernel that does the work" of uhc_batch_kernel_time
+static int launch_timed(UhcBatch* b, const EvPair* ev, int mode, int tier, const KernelArgs* K, const double* d_action, const double* d_tbase, const int* d_active, size_t lds_bytes) {
+    if (ev) HIP_OK(hipEventRecord(ev->first, b->stream));
+    HIP_OK(uhc_launch_step(mode, tier, K, d_action, d_tbase, d_active, lds_bytes, b->stream));
+    if (ev) { HIP_OK(hipEventRecord(ev->second, b->stream)); b->ev_used.push_back(*ev); }
+    return 0;
+}
+
 // sticky tiers: an env starts in the tier that computed its last step.  The general / large tiers' own envs run on a side stream
 // BESIDE the fast tier (their launches last several times longer per env; in a chain behind it the step would wait for them);
 // only the envs a tier hands on this very step go through the chain.  All launches filter on one snapshot of the tier table.
-// The sizes of the consumer launches come from the newest queue counts the host has seen: plan_sticky_step (uhc_plan.cpp).
-static int launch_sticky(UhcBatch* b, int mode, const double* d_action, const double* d_tbase, const int* d_active, bool timed, std::pair<hipEvent_t, hipEvent_t> ev) {
-    const bool big = b->A.last_tier >= 3;
-        KernelArgs K = b->A;
-        // tier 4's own consumers: when the newest counts seen say that envs went through tier 4 (counts[7]: hand-ons of the large tier + envs that start there),
-        // a few persistent workgroups wait on a queue of their own (d_lists + 2 n_env) beside everything else, and the large tier's consumers append what
-        // they find too big instead of leaving it for the chained launch at the very end of the step -- where a 10 ms env-step of one env used to be added
-        // to every step in which any env needed tier 4 (configs[4]: 64 k -> 42 k env-steps/s when tier 4 came in).  Envs that START in tier 4
-        // (UHC_DEBUG bit 12) are put at the head of that queue by the list kernel.
-        int est4 = 0, est2_then = 0;
-        if (b->A.last_tier == 4 && b->q4_max > 0)
-            for (long long k = b->cnt_step - 1; k >= 0 && k > b->cnt_step - 8; k--)
-                if (hipEventQuery(b->cnt_ev[k % 8]) == hipSuccess) { est4 = b->h_counts[8 * (k % 8) + 7]; est2_then = b->h_counts[8 * (k % 8) + 2]; break; }
-        (void)hipGetLastError();
+// Which launches a step has, their sizes and how their queues are wired is decided by plan_sticky_step / sticky_wiring (uhc_plan.cpp) from
+// the newest queue counts the host has seen; what follows is the device work.
+
+// How long the queues got is known on the host with a lag (asynchronous copies of the final counts, never waited for): the newest row of
+// h_counts that has landed -> its step in *step --, or null while none of the last seven steps' has.
+static const int* newest_counts(UhcBatch* b, long long* step) {
+    const int* row = nullptr;
+    for (long long k = b->cnt_step - 1; k >= 0 && k > b->cnt_step - 8 && !row; k--)
+        if (hipEventQuery(b->cnt_ev[k % 8]) == hipSuccess) { row = b->h_counts + UHC_N_WORDS * (k % 8); *step = k; }
+    (void)hipGetLastError();  // (a query that says "not ready" is no error of the step)
+    return row;
+}
+// The back-off.  A consumer gave up waiting: its producers did not run beside it (or too slowly).  No waiting consumers for the next 32
+// steps; after the third time, for good.
+static void update_back_off(UhcBatch* b, int give_ups) {
+    if (give_ups > b->aborts_seen) {
+        b->aborts_seen = give_ups;
+        b->queues_off_until = ++b->abort_events >= 3 ? (long long)1 << 62 : b->cnt_step + 32;
+    }
+    b->queues_off = b->cnt_step < b->queues_off_until;
+}
+// the KernelArgs of one entry of the step's table: the batch's, with the entry's slots resolved against the batch's lists / counts / cursors / fin.
+// A field the entry does not name is null or zero -- also where the launch before it on the host had it set: n_wait, spares, prod_fin and prod_total are
+// read by queue_claim alone and `started` by uhc_step_queue_kernel alone (uhc_physics_impl.h), the kernel of a launch that has a list.
+static KernelArgs wire_launch(const UhcBatch* b, const StepLaunch& L, int sticky_mask) {
+    auto at = [](int* base, int slot, size_t stride) { return slot == UHC_NONE ? nullptr : base + slot * stride; };
+    const size_t E = b->n_env;
+    KernelArgs K = b->A;
+    K.cnt4 = b->d_counts + UHC_CNT_T4_STEPS;
+    K.sticky_mask = sticky_mask;
+    K.tier_want = L.tier_want;
+    K.list = at(b->d_lists, L.list, E); K.list_count = at(b->d_counts, L.count, 1); K.list_cursor = at(b->d_cursors, L.cursor, 1);
+    K.grid = (L.list != UHC_NONE || L.chunk) ? L.grid : 0;  // (0: one workgroup per env, the whole-step launch)
+    K.n_wait = L.n_wait; K.spares = at(b->d_fin, L.spares, 1); K.started = at(b->d_fin, L.started, 1);
+    K.prod_fin = at(b->d_fin, L.prod_fin, 1); K.prod_total = L.prod_total;
+    K.fin = at(b->d_fin, L.fin, 1);
+    K.q_next = at(b->d_lists, L.next_list, E); K.q_next_count = at(b->d_counts, L.next_count, 1);
+    K.chunk = L.chunk;
+    K.order = L.use_order ? b->d_order : nullptr;  // (null with UHC_DEBUG bit 3: env order)
+    return K;
+}
+static int launch_sticky(UhcBatch* b, int mode, const double* d_action, const double* d_tbase, const int* d_active, const EvPair* ev) {
     StickyInputs in{};
-    in.est4 = est4; in.est2_then = est2_then; in.n_env = b->n_env; in.n_cu = b->n_cu; in.lds_bytes_fast = b->lds_bytes_fast; in.large_first = b->large_first;
-    in.fast_chunk = b->fast_chunk; in.n_substeps = b->A.c.n_substeps;
-    in.last_tier = b->A.last_tier; in.q2_div = b->q2_div; in.q2_wait_min = b->q2_wait_min; in.q2_max = b->q2_max; in.q3_max = b->q3_max; in.q4_max = b->q4_max;
+    in.n_env = b->n_env; in.n_cu = b->n_cu; in.lds_bytes_fast = b->lds_bytes_fast; in.large_first = b->large_first;
+    in.fast_chunk = b->fast_chunk; in.n_substeps = b->A.c.n_substeps; in.last_tier = b->A.last_tier; set_caps(in, b->caps);
 #ifdef UHC_EXPERIMENTS
     in.fixed_cap2 = (b->A.dbg & 2048) != 0;  // (measurement switch: a fixed cap UHC_Q2_MAX on the general tier's consumers)
 #endif
-    // (the list kernel's view of tier 4's consumers: decided before the back-off bookkeeping below, like the counts it is sized from)
-    in.queues_off = b->queues_off;
-    const bool launch4 = plan_sticky_step(in).launch4;
-        K.cnt4 = b->d_counts + 7;
-        HIP_OK(uhc_launch_tier_lists(b->A.s.tier, d_active, b->n_env, b->tier_now, b->d_lists, b->d_counts, b->d_cursors, b->d_fin, b->A.s.cost, b->A.s.fresh, b->d_order,
-                                     launch4 ? 1 : 0, b->A.s.pend3, b->stream));
-        HIP_OK(hipEventRecord(b->ev_fork, b->stream));
-        // how long the queues got is known on the host with a lag (asynchronous copies of the final counts, never waited for): the newest
-        // copy that has landed sizes this step's consumer launches.  While the general tier's queue was empty when last seen there are no
-        // consumers at all: an env the fast tier hands on is flagged and goes through the chained launches like in mode 0.
-        // (the host may not run more than two steps ahead of the device here: a launch sized for a queue of five that meets nine hundred
-        //  envs works them off five at a time)
-        if (b->cnt_step >= 2) HIP_OK(hipEventSynchronize(b->cnt_ev[(b->cnt_step - 2) % 8]));
-        int est2 = 0, est3 = 0, handed2 = 0;  // queue lengths at the end of the newest step seen, and how many of the general tier's came in during the step
-        for (long long k = b->cnt_step - 1; k >= 0 && k > b->cnt_step - 8; k--)
-            if (hipEventQuery(b->cnt_ev[k % 8]) == hipSuccess) {
-                const int* hc = b->h_counts + 8 * (k % 8);
-                est2 = hc[2]; est3 = hc[3]; handed2 = std::max(0, hc[2] - hc[4]);
-                if (b->A.dbg & 64) fprintf(stderr, "uhc step %lld: queues %d / %d envs (%d handed on), gate waited %.1f us, gave up %d, queues_off %d\n", k, est2, est3, handed2, 0.01 * hc[1], hc[0], (int)b->queues_off);
-                if (hc[0] > b->aborts_seen) {  // a consumer gave up waiting: its producers did not run beside it (or too slowly).  No waiting
-                    b->aborts_seen = hc[0];     // consumers for the next 32 steps; after the third time, for good
-                    b->queues_off_until = ++b->abort_events >= 3 ? (long long)1 << 62 : b->cnt_step + 32;
-                }
-                b->queues_off = b->cnt_step < b->queues_off_until;
-                break;
-            }
-    in.est2 = est2; in.est3 = est3; in.handed2 = handed2; in.queues_off = b->queues_off;
-    const StickySizes z = plan_sticky_step(in);
-    const bool queues = z.queues, waiting = z.waiting, q3 = z.q3, q4 = launch4 && q3;
-    const int grid2 = z.grid2, grid3 = z.grid3, grid4 = z.grid4;
-    K.sticky_mask = (queues ? 4 : 0) | (q3 ? 8 : 0) | (launch4 ? 16 : 0);
-        if (q4) {  // (first of the side launches: a whole CU's LDS each, only to be had before the fast tier's launch has filled the chip)
-            HIP_OK(hipStreamWaitEvent(b->side_stream4, b->ev_fork, 0));
-            K.tier_want = 0; K.list = b->d_lists + 2 * b->n_env; K.list_count = b->d_counts + 6; K.list_cursor = b->d_cursors + 4;
-            K.grid = grid4; K.n_wait = grid4; K.spares = nullptr; K.started = nullptr;
-            K.prod_fin = b->d_fin + 5; K.prod_total = grid3;  // the large tier's consumers
-            K.fin = nullptr; K.q_next = nullptr; K.q_next_count = nullptr;
-            if (b->A.dbg & 64) fprintf(stderr, "uhc step %lld: %d tier-4 consumers (%d env-steps went through tier 4 when last seen)\n", b->cnt_step, grid4, est4);
-            HIP_OK(uhc_launch_step(mode, 4, &K, d_action, d_tbase, nullptr, b->lds_bytes_big, b->side_stream4));
-            HIP_OK(hipEventRecord(b->ev_side3, b->side_stream4));
-        }
-        auto launch_large = [&]() -> int {
-            HIP_OK(hipStreamWaitEvent(b->side_stream3, b->ev_fork, 0));
-            K.tier_want = 0; K.list = b->d_lists + b->n_env; K.list_count = b->d_counts + 3; K.list_cursor = b->d_cursors + 3;
-            K.grid = grid3; K.n_wait = grid3; K.spares = nullptr; K.started = b->d_fin + 4;
-            K.prod_fin = b->d_fin + 2; K.prod_total = grid2;  // the general tier's workgroups: they never wait for this launch
-            K.fin = q4 ? b->d_fin + 5 : nullptr; K.q_next = q4 ? b->d_lists + 2 * b->n_env : nullptr; K.q_next_count = q4 ? b->d_counts + 6 : nullptr;
-            HIP_OK(uhc_launch_step(mode, 3, &K, d_action, d_tbase, nullptr, b->lds_bytes_big, b->side_stream3));
-            HIP_OK(hipEventRecord(b->ev_side2, b->side_stream3));
-            return 0;
-        };
-        // (the large tier's consumers first where their stream has a queue pool of its own: whole CUs are only free while nothing else is
-        //  resident, so the general tier's launch waits behind a gate until they have reported in)
-        if (q3 && b->large_first) { if (launch_large()) return -1; }
-        if (queues) {
-            HIP_OK(hipStreamWaitEvent(b->side_stream, b->ev_fork, 0));
-            if (q3 && b->large_first && !(b->A.dbg & 32)) HIP_OK(uhc_launch_gate(b->d_fin + 4, grid3, nullptr, nullptr, b->side_stream));
-            K.tier_want = 0; K.list = b->d_lists; K.list_count = b->d_counts + 2; K.list_cursor = b->d_cursors + 2;
-            K.grid = grid2;
-            K.prod_fin = waiting ? b->d_fin + 1 : nullptr; K.prod_total = z.fast.prod_total;  // every workgroup of the fast tier's launch below
-            K.fin = b->d_fin + 2; K.started = waiting ? b->d_fin + 3 : nullptr;
-            K.n_wait = z.n_wait; K.spares = b->d_fin;
-            K.q_next = q3 ? b->d_lists + b->n_env : nullptr; K.q_next_count = q3 ? b->d_counts + 3 : nullptr;
-            HIP_OK(uhc_launch_step(mode, 2, &K, d_action, d_tbase, nullptr, b->lds_bytes, b->side_stream));
-            HIP_OK(hipEventRecord(b->ev_side1, b->side_stream));
-        }
-        if (q3 && !b->large_first) { if (launch_large()) return -1; }
-        K.list = nullptr; K.list_count = nullptr; K.list_cursor = nullptr; K.grid = 0; K.prod_fin = nullptr; K.prod_total = 0; K.started = nullptr; K.spares = nullptr;
-        // The fast tier's launch fills every CU's LDS the moment it starts; consumers that are not resident by then get theirs only when
-        // its first workgroups leave (the tier trace showed them starting 3.7 ms into the step).  A one-thread gate on this stream holds
-        // the launch back until every consumer workgroup has reported in (or 200 us have passed).
-        if (waiting && !(b->A.dbg & 32)) HIP_OK(uhc_launch_gate(b->d_fin + 3, grid2, b->d_counts + 1,
-                                                                     (b->A.dbg & 16) ? b->A.s.prof + (size_t)(b->n_env - 1) * 40 + 16 : nullptr, b->stream));
-        K.tier_want = 1;
-        K.chunk = z.fast.chunk; K.grid = z.fast.chunk ? z.fast.grid : 0;  // (in substep chunks: n_chunks x n_env workgroups, chunk-major by ticket)
-        K.order = b->d_order;  // (costliest envs first; null with UHC_DEBUG bit 3: env order)
-        K.fin = waiting ? b->d_fin + 1 : nullptr;
-        K.q_next = waiting ? b->d_lists : nullptr; K.q_next_count = waiting ? b->d_counts + 2 : nullptr;
-        if (timed) HIP_OK(hipEventRecord(ev.first, b->stream));
-        HIP_OK(uhc_launch_step(mode, 1, &K, d_action, d_tbase, d_active, b->lds_bytes_fast, b->stream));
-        if (timed) { HIP_OK(hipEventRecord(ev.second, b->stream)); b->ev_used.push_back(ev); }
-        K.tier_want = 0; K.sticky_mask = 0; K.fin = nullptr; K.q_next = nullptr; K.q_next_count = nullptr; K.order = nullptr; K.chunk = 0; K.grid = 0;
-        // chained launches on what is still flagged: everything handed on when no consumers run, nothing (two empty launches) when they do
-        if (queues) HIP_OK(hipStreamWaitEvent(b->stream, b->ev_side1, 0));
-        HIP_OK(uhc_launch_step(mode, 2, &K, d_action, d_tbase, b->A.s.pend2, b->lds_bytes, b->stream));
-        if (q3) HIP_OK(hipStreamWaitEvent(b->stream, b->ev_side2, 0));
-        if (q4) HIP_OK(hipStreamWaitEvent(b->stream, b->ev_side3, 0));
-        if (big) HIP_OK(uhc_launch_step(mode, 3, &K, d_action, d_tbase, b->A.s.pend3, b->lds_bytes_big, b->stream));
-        // the final queue lengths of this step, for the steps to come
-        const int slot = (int)(b->cnt_step % 8);
-        HIP_OK(hipMemcpyAsync(b->d_counts, b->A.s.q_abort, sizeof(int), hipMemcpyDeviceToDevice, b->stream));  // counts[0] carries the give-up count
-        HIP_OK(hipMemcpyAsync(b->h_counts + 8 * slot, b->d_counts, 8 * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-        HIP_OK(hipEventRecord(b->cnt_ev[slot], b->stream));
-        b->cnt_step++;
-        return 0;
+    long long seen = 0;
+    // tier 4's consumers: the list kernel fills their queue, so this is decided first -- before the back-off bookkeeping below, like the counts it is sized from
+    if (b->A.last_tier == 4 && b->caps.q4_max > 0)
+        if (const int* hc = newest_counts(b, &seen)) { in.est4 = hc[UHC_CNT_T4_STEPS]; in.est2_then = hc[UHC_CNT_GEN]; }
+    const bool launch4 = sticky_launch4(in.last_tier, in.est4, in.est2_then, b->queues_off);
+    HIP_OK(uhc_launch_tier_lists(b->A.s.tier, d_active, b->n_env, b->tier_now, b->d_lists, b->d_counts, b->d_cursors, b->d_fin, b->A.s.cost, b->A.s.fresh, b->d_order,
+                                 launch4 ? 1 : 0, b->A.s.pend3, b->stream));
+    HIP_OK(hipEventRecord(b->ev_fork, b->stream));
+    // The newest counts that have landed size this step's consumer launches.  While the general tier's queue was empty when last seen there
+    // are no consumers at all: an env the fast tier hands on is flagged and goes through the chained launches like in mode 0.
+    // (the host may not run more than two steps ahead of the device here: a launch sized for a queue of five that meets nine hundred
+    //  envs works them off five at a time)
+    if (b->cnt_step >= 2) HIP_OK(hipEventSynchronize(b->cnt_ev[(b->cnt_step - 2) % 8]));
+    if (const int* hc = newest_counts(b, &seen)) {
+        // queue lengths at the end of the newest step seen, and how many of the general tier's came in during the step
+        in.est2 = hc[UHC_CNT_GEN]; in.est3 = hc[UHC_CNT_BIG]; in.handed2 = std::max(0, hc[UHC_CNT_GEN] - hc[UHC_CNT_GEN_HEAD]);
+        if (b->A.dbg & 64)
+            fprintf(stderr, "uhc step %lld: queues %d / %d envs (%d handed on), gate waited %.1f us, gave up %d, queues_off %d\n", seen, in.est2, in.est3, in.handed2,
+                    0.01 * hc[UHC_CNT_GATE_WAIT], hc[UHC_CNT_GIVE_UPS], (int)b->queues_off);
+        update_back_off(b, hc[UHC_CNT_GIVE_UPS]);
     }
+    in.queues_off = b->queues_off;
+    const StickySizes z = plan_sticky_step(in, launch4);
+    const StepWiring w = sticky_wiring(z, b->large_first);
+    const hipStream_t streams[4] = {b->stream, b->side_stream, b->side_stream3, b->side_stream4};   // by StepStream
+    const hipEvent_t joins[4] = {nullptr, b->ev_side1, b->ev_side2, b->ev_side3};                  // a side stream's launch done: the chain waits for it
+    const size_t lds[5] = {0, b->lds_bytes_fast, b->lds_bytes, b->lds_bytes_big, b->lds_bytes_big};  // by tier
+    for (int k = 0; k < w.n; k++) {
+        const StepLaunch& L = w.launch[k];
+        const hipStream_t st = streams[L.stream];
+        const bool side = L.stream != STREAM_MAIN;
+        if (side) HIP_OK(hipStreamWaitEvent(st, b->ev_fork, 0));
+        if (L.gate_started != UHC_NONE && !(b->A.dbg & 32))  // (UHC_DEBUG bit 5: no gates; bit 4: the trace of the gate that reports its wait, in the record of the last env)
+            HIP_OK(uhc_launch_gate(b->d_fin + L.gate_started, L.gate_want, L.gate_waited != UHC_NONE ? b->d_counts + L.gate_waited : nullptr,
+                                   (L.gate_waited != UHC_NONE && (b->A.dbg & 16)) ? b->A.s.prof + (size_t)(b->n_env - 1) * UHC_NPROF + 16 : nullptr, st));
+        if (L.tier == 4 && (b->A.dbg & 64)) fprintf(stderr, "uhc step %lld: %d tier-4 consumers (%d env-steps went through tier 4 when last seen)\n", b->cnt_step, L.grid, in.est4);
+        const KernelArgs K = wire_launch(b, L, z.sticky_mask);
+        if (side) {
+            HIP_OK(uhc_launch_step(mode, L.tier, &K, d_action, d_tbase, nullptr, lds[L.tier], st));
+            HIP_OK(hipEventRecord(joins[L.stream], st));
+        } else TRY(launch_timed(b, ev, mode, L.tier, &K, d_action, d_tbase, d_active, lds[L.tier]));
+    }
+    // chained launches on what is still flagged: everything handed on when no consumers run, nothing (two empty launches) when they do
+    KernelArgs K = b->A;
+    K.cnt4 = b->d_counts + UHC_CNT_T4_STEPS;
+    if (z.queues) HIP_OK(hipStreamWaitEvent(b->stream, b->ev_side1, 0));
+    HIP_OK(uhc_launch_step(mode, 2, &K, d_action, d_tbase, b->A.s.pend2, b->lds_bytes, b->stream));
+    if (z.q3) HIP_OK(hipStreamWaitEvent(b->stream, b->ev_side2, 0));
+    if (z.q4) HIP_OK(hipStreamWaitEvent(b->stream, b->ev_side3, 0));
+    if (b->A.last_tier >= 3) HIP_OK(uhc_launch_step(mode, 3, &K, d_action, d_tbase, b->A.s.pend3, b->lds_bytes_big, b->stream));
+    // the final queue lengths of this step, for the steps to come
+    const int slot = (int)(b->cnt_step % 8);
+    HIP_OK(hipMemcpyAsync(b->d_counts + UHC_CNT_GIVE_UPS, b->A.s.q_abort, sizeof(int), hipMemcpyDeviceToDevice, b->stream));
+    HIP_OK(hipMemcpyAsync(b->h_counts + UHC_N_WORDS * slot, b->d_counts, UHC_N_WORDS * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    HIP_OK(hipEventRecord(b->cnt_ev[slot], b->stream));
+    b->cnt_step++;
+    return 0;
+}
 
 // fast kernel on every (active) env, then the general kernel on the envs that raised redo
 static int launch(UhcBatch* b, int mode, const double* d_action, const double* d_tbase, const int* d_active) {
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    EvPair pair{nullptr, nullptr};
     const bool timed = b->timing && mode == 0;  // HIP events around the kernel that does the work of a control step
     if (timed) {
-        if (b->ev_free.empty()) { HIP_OK(hipEventCreate(&ev.first)); HIP_OK(hipEventCreate(&ev.second)); }
-        else { ev = b->ev_free.back(); b->ev_free.pop_back(); }
+        if (b->ev_free.empty()) { HIP_OK(hipEventCreate(&pair.first)); HIP_OK(hipEventCreate(&pair.second)); }
+        else { pair = b->ev_free.back(); b->ev_free.pop_back(); }
     }
+    const EvPair* ev = timed ? &pair : nullptr;
     const bool general = b->general_only;
     const bool big = b->A.last_tier >= 3;  // (tier 4 has no chained launch of its own: the large tier's workgroups go on with it; under sticky tiers it has queue consumers)
     // tier chain: every tier works on the envs the previous one flagged (redo / redo2) and left untouched
-    HIP_OK(hipMemsetAsync(b->A.s.redo, 0, sizeof(int) * ((size_t)b->n_env * 6 + 1), b->stream));  // redo (the step's UHC_F_REDO words), pend2, pend3, resume, why, chunk_done, ticket: one allocation
+    HIP_OK(hipMemsetAsync(b->A.s.redo, 0, sizeof(int) * step_words(b->n_env).total, b->stream));
     // (inside a stream capture the sticky launch cannot be used: it sizes its consumer launches from counts the host reads between steps
     //  -- event queries and a wait that are not allowed while capturing, and a replay would repeat the capture step's sizes anyway.  A
     //  captured step takes the plain tier chain, which computes the same step.)
@@ -532,22 +533,16 @@ static int launch(UhcBatch* b, int mode, const double* d_action, const double* d
         if (hipStreamIsCapturing(b->stream, &cs) == hipSuccess) capturing = cs == hipStreamCaptureStatusActive;
         else (void)hipGetLastError();
     }
-    if (mode == 0 && b->path_mode == 2 && b->use_fast && !general && !capturing) return launch_sticky(b, mode, d_action, d_tbase, d_active, timed, ev);
+    if (mode == 0 && b->path_mode == 2 && b->use_fast && !general && !capturing) return launch_sticky(b, mode, d_action, d_tbase, d_active, ev);
     if (b->use_fast && !general) {
-        if (timed) HIP_OK(hipEventRecord(ev.first, b->stream));
         KernelArgs K = b->A;
         if (mode == 0) {  // the control step in substep chunks (the forward-only and kinematics launches have no substeps)
             const FastChunks f = plan_fast_chunks(K.c.n_substeps, default_fast_chunk(b->fast_chunk, K.c.n_substeps, b->n_env, b->n_cu, b->lds_bytes_fast), b->n_env);
             K.chunk = f.chunk; K.grid = f.chunk ? f.grid : 0;
         }
-        HIP_OK(uhc_launch_step(mode, 1, &K, d_action, d_tbase, d_active, b->lds_bytes_fast, b->stream));
-        if (timed) { HIP_OK(hipEventRecord(ev.second, b->stream)); b->ev_used.push_back(ev); }
+        TRY(launch_timed(b, ev, mode, 1, &K, d_action, d_tbase, d_active, b->lds_bytes_fast));
         HIP_OK(uhc_launch_step(mode, 2, &b->A, d_action, d_tbase, b->A.s.pend2, b->lds_bytes, b->stream));
-    } else {
-        if (timed) HIP_OK(hipEventRecord(ev.first, b->stream));
-        HIP_OK(uhc_launch_step(mode, 2, &b->A, d_action, d_tbase, d_active, b->lds_bytes, b->stream));
-        if (timed) { HIP_OK(hipEventRecord(ev.second, b->stream)); b->ev_used.push_back(ev); }
-    }
+    } else TRY(launch_timed(b, ev, mode, 2, &b->A, d_action, d_tbase, d_active, b->lds_bytes));
     if (big) HIP_OK(uhc_launch_step(mode, 3, &b->A, d_action, d_tbase, b->A.s.pend3, b->lds_bytes_big, b->stream));
     return 0;
 }

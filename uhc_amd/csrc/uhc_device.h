@@ -38,6 +38,34 @@
 #define UHC_WHY_SOLVER (1 << 21)  // the working sets of the general / large tier did not finish (more than 64 force-carrying rows in an island, no convergence): Newton on the primal takes over
 #define UHC_MINVAL 1e-15
 #define UHC_MAXVAL 1e10
+#define UHC_NPROF 40  // int64 words per env of the stage-profile record (UHC_F_STAGE_PROF)
+
+// Sticky tiers: the words through which a step's launches find each other.  Four small int arrays of the batch -- the env queues `lists`
+// [UHC_N_LISTS][n_env], and `counts`, `cursors`, `fin` of UHC_N_WORDS ints each -- are reset by the list kernel at the head of the step
+// (uhc_tier_lists_kernel) and wired into the launches' KernelArgs by the host from the step's table of launches (sticky_wiring, uhc_plan.h).
+#define UHC_N_WORDS 8
+enum UhcList { UHC_LIST_GEN = 0, UHC_LIST_BIG = 1, UHC_LIST_T4 = 2, UHC_N_LISTS = 3 };  // the queues of the general / large tier's and tier 4's consumers
+enum UhcCount {  // counts (and every row of the host's lagged copies of it, UhcBatch::h_counts)
+    UHC_CNT_GIVE_UPS = 0,   // consumers that gave up waiting (DevState::q_abort[0], copied in at the end of the step: the host backs off)
+    UHC_CNT_GATE_WAIT = 1,  // 100 MHz ticks the gate before the fast tier's launch waited (diagnostic)
+    UHC_CNT_GEN = 2,        // entries of the general tier's queue so far
+    UHC_CNT_BIG = 3,        // ... of the large tier's
+    UHC_CNT_GEN_HEAD = 4,   // the same two as the step began (the host compares with how they end)
+    UHC_CNT_BIG_HEAD = 5,
+    UHC_CNT_T4 = 6,         // entries of tier 4's queue so far
+    UHC_CNT_T4_STEPS = 7    // the step's tier-4 env-steps: envs that start there + every hand-on to tier 4 (KernelArgs::cnt4); sizes the NEXT steps' tier-4 consumers
+};
+enum UhcCursor { UHC_CUR_GEN = 2, UHC_CUR_BIG = 3, UHC_CUR_T4 = 4 };  // cursors: the next entry of a queue to be claimed
+enum UhcFin {  // fin: counters the workgroups of a launch bump once each
+    UHC_FIN_SPARES = 0,  // seats taken by general-tier consumers that wait for hand-ons (KernelArgs::spares)
+    UHC_FIN_FAST = 1,    // workgroups of the fast tier's launch that have left
+    UHC_FIN_GEN = 2,     // general-tier consumers that have left
+    UHC_FIN_GEN_IN = 3,  // general-tier consumers resident (KernelArgs::started: the gate before the fast tier's launch waits for them)
+    UHC_FIN_BIG_IN = 4,  // large-tier consumers resident (the gate before the general tier's launch, where the large tier's goes first)
+    UHC_FIN_BIG = 5      // large-tier consumers that have left
+};
+static_assert(UHC_CNT_BIG == UHC_CNT_GEN + 1 && UHC_CNT_BIG_HEAD == UHC_CNT_GEN_HEAD + 1 && UHC_LIST_BIG == UHC_LIST_GEN + 1,
+              "the list kernel indexes the general / large tier's words by tier - 2");
 
 // topology + options: identical for every env of a batch
 struct DevTopo {
@@ -122,7 +150,7 @@ struct DevState {  // HBM, env-major
     int* cost;   // per env: how close its last step came to the fast tier's capacity, in sixty-fourths (orders the fast tier's launch)
     int* fresh;  // 1: the env was restarted on the device (set_state done, kinematics refreshed); its mj_forward runs at the head of its next step
     const int* env_model;
-    long long* prof;  // [n_env][16] stage cycle accumulators (only written by -DUHC_STAGE_PROF builds)
+    long long* prof;  // [n_env][UHC_NPROF] stage cycle accumulators (only written by -DUHC_STAGE_PROF builds)
     unsigned long long* path_stats;  // running counts of control steps (MODE 0): [0] envs the fast kernel handed on, [1] envs the general kernel
                                      // computed that would have fitted the fast one, [2] envs the general kernel computed (uhc_batch_set_kernel_path 2)
     const double* model_blob;
@@ -200,7 +228,7 @@ struct KernelArgs {
                    // four-wave consumers' queue, and stays there while it peaks above 3/4 of the mark (0: never; UHC_T4_ROWS)
     int truncate;  // fast kernel: drop contacts / rows beyond its capacity instead of handing the env to the general kernel
     int ball_limits;  // the model has limited ball joints: the fast tier launches its DENSE instantiation (which carries the ball-limit rows)
-    int dbg;                 // debug switches (UHC_DEBUG env var): bit 0 = working sets never merge islands, bit 1 = MPR vertices not staged in LDS, bit 2 = a handed-on env restarts its step instead of resuming at the substep, bit 3 = sticky fast tier launches in env order, bit 4 = tier trace in the stage-profile record, bit 5 = no gate before the fast tier's launch, bit 6 = log the queue lengths and the gate's wait per step, bit 7 = no box cull of the convex pairs, bit 8 (256) = the general tier's first working set is NOT filled by rank (k_as_general; A/B of DESIGN 2), bits 9 / 10 (512 / 1024) = fill 48 / 56 lanes instead of 64, bit 11 (2048) = fixed cap UHC_Q2_MAX on the general tier's consumers (launch()).  bit 12 (4096) = sticky tier 4: an env whose step ended in tier 4 starts its next step there, at the head of the tier-4 consumers' queue (uhc_capi.cpp launch(); measured and not the default, see uhc_step_env).  Bits 8-12 change which envs report windows / sweeps in UHC_F_REDO: measurement switches that exist only in libraries built with -DUHC_EXPERIMENTS (tools/ A/B builds) -- the shipped library compiles their reads out (UHC_EXP in uhc_physics_impl.h) and masks the bits (uhc_capi.cpp); uhc_build_flags() bit 0 tells which kind a library is
+    int dbg;                 // debug switches (UHC_DEBUG env var): bit 0 = working sets never merge islands, bit 1 = MPR vertices not staged in LDS, bit 2 = a handed-on env restarts its step instead of resuming at the substep, bit 3 = sticky fast tier launches in env order, bit 4 = tier trace in the stage-profile record, bit 5 = no gate before the fast tier's launch, bit 6 = log the queue lengths and the gate's wait per step, bit 7 = no box cull of the convex pairs, bit 8 (256) = the general tier's first working set is NOT filled by rank (k_as_general; A/B of DESIGN 2), bits 9 / 10 (512 / 1024) = fill 48 / 56 lanes instead of 64, bit 11 (2048) = fixed cap UHC_Q2_MAX on the general tier's consumers (plan_sticky_step, uhc_plan.cpp).  bit 12 (4096) = sticky tier 4: an env whose step ended in tier 4 starts its next step there, at the head of the tier-4 consumers' queue (uhc_tier_lists_kernel; uhc_capi.cpp launch_sticky(); measured and not the default, see uhc_step_env).  Bits 8-12 change which envs report windows / sweeps in UHC_F_REDO: measurement switches that exist only in libraries built with -DUHC_EXPERIMENTS (tools/ A/B builds) -- the shipped library compiles their reads out (UHC_EXP in uhc_physics_impl.h) and masks the bits (uhc_capi.cpp); uhc_build_flags() bit 0 tells which kind a library is
     int nvp;                 // stride of a dense row (nv rounded up to 2 doubles)
     int adjdeg;              // stride of the per-model hull adjacency table (largest vertex degree over the batch's models)
     DevCtrl c;

@@ -26,6 +26,19 @@ struct UhcModel {
 };
 
 // ------------------------------------------------------------------ batch
+// the caps on the sticky tiers' consumer launches (UHC_Q* knobs: read_knobs -> the batch -> plan_sticky_step)
+struct QueueCaps {
+    int q2_div = 1;        // waiting general-tier consumers per expected env: 1 / q2_div (UHC_Q2_DIV >= 1)
+    int q2_wait_min = 16;  // at least so many general-tier consumers wait for hand-ons (UHC_Q2_WAIT >= 1)
+    int q2_max = 256;      // most general-tier consumers beside a fast tier that still has most of the envs (UHC_Q2_MAX >= 16)
+    int q3_max = 32;       // most large-tier consumers in that regime (UHC_Q3_MAX >= 2)
+    int q4_max = 16;       // most tier-4 consumers (UHC_Q4_MAX >= 0; 0: none -- what the large tier hands on waits for the chained launch at the end of the step)
+};
+// the per-step words of a batch: seven int arrays in ONE allocation that starts at DevState::redo (the step's UHC_F_REDO words) and that launch() clears with
+// one memset per step.  Offsets in ints from redo; ticket is one word, the others have one per env.
+struct StepWords { size_t pend2, pend3, resume, why, chunk_done, ticket, total; };
+inline StepWords step_words(size_t n_env) { return {n_env, 2 * n_env, 3 * n_env, 4 * n_env, 5 * n_env, 6 * n_env, 6 * n_env + 1}; }
+
 struct UhcBatch {
     int n_env = 0, device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -46,15 +59,11 @@ struct UhcBatch {
     int* d_order = nullptr;  // launch order of the fast tier under sticky tiers (uhc_tier_lists_kernel)
     int aborts_seen = 0, abort_events = 0;
     long long queues_off_until = 0;
-    int q2_wait_min = 16;    // at least so many general-tier consumers wait for hand-ons (UHC_Q2_WAIT)
-    int q2_div = 1;          // waiting general-tier consumers per expected env: 1 / q2_div (UHC_Q2_DIV)
-    int q2_max = 256;        // most general-tier consumers beside a fast tier that still has most of the envs (UHC_Q2_MAX)
-    int q4_max = 16;         // most tier-4 consumers (UHC_Q4_MAX; 0: none -- what the large tier hands on waits for the chained launch at the end of the step)
-    int q3_max = 32;         // most large-tier consumers in that regime (UHC_Q3_MAX)
+    QueueCaps caps;
     int fast_chunk = 0;      // substeps per chunk of the fast tier's control step (UHC_FAST_CHUNK; 0: default_fast_chunk decides)
-    int *d_lists = nullptr, *d_counts = nullptr, *d_cursors = nullptr, *d_fin = nullptr;
+    int *d_lists = nullptr, *d_counts = nullptr, *d_cursors = nullptr, *d_fin = nullptr;  // the queues' words: UhcList / UhcCount / UhcCursor / UhcFin (uhc_device.h)
     bool queues_off = false;
-    int* h_counts = nullptr;  // pinned [8][8]: give-ups, gate wait, final queue lengths [2], [3], queue lengths at the head of the step [4], [5]; the last steps', copied back asynchronously
+    int* h_counts = nullptr;  // pinned [8][UHC_N_WORDS]: d_counts as the last eight steps left it (rows indexed by UhcCount), copied back asynchronously
     hipEvent_t cnt_ev[8] = {};
     long long cnt_step = 0;
     std::vector<void*> allocs;
@@ -66,5 +75,5 @@ struct UhcBatch {
     int n_trailing_free = 0;  // free bodies at the end of the model (objects)
     bool hbm_guard = false;  // UHC_GUARD_LDS=1 / 2: zero-initialised device arrays sit between fences (dalloc)
     struct Field { void* ptr; int64_t count; };
-    Field field[21] = {};  // uhc_batch_field: UHC_F_* -> (device pointer, elements)
+    Field field[UHC_F_COST + 1] = {};  // uhc_batch_field: UHC_F_* -> (device pointer, elements)
 };

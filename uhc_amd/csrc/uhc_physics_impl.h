@@ -33,7 +33,7 @@ extern __shared__ __attribute__((aligned(16))) double smem[];
 #define LANE ((int)threadIdx.x)
 #endif
 // optional per-stage cycle accounting (build with -DUHC_STAGE_PROF; see tools/stage_profile.py)
-#define UHC_NPROF 40  // int64 words per env of the stage-profile record (UHC_F_STAGE_PROF)
+// (the record's size, UHC_NPROF, is in uhc_device.h: the host allocates it)
 #ifdef UHC_STAGE_PROF
 #define PROF_DECL long long pt_[UHC_NPROF] = {}; long long pt_last_ = __builtin_readcyclecounter();
 #define PROF_ARGS , long long* pt_, long long& pt_last_

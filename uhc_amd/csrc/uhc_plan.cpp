@@ -668,12 +668,19 @@ int default_fast_chunk(int knob, int n_substeps, int n_env, int n_cu, size_t lds
 }
 
 // ------------------------------------------------------------------ sticky tiers: one step's consumer launches
-StickySizes plan_sticky_step(const StickyInputs& in) {
+// tier 4's own consumers: when the newest counts seen say that envs went through tier 4 (est4: hand-ons of the large tier + envs that start there) while the
+// general tier had a queue (est2_then: the consumers need the large tier's beside them, which run whenever the general tier's do), a few persistent workgroups
+// wait on a queue of their own beside everything else, and the large tier's consumers append what they find too big instead of leaving it for the chained
+// launch at the very end of the step -- where a 10 ms env-step of one env used to be added to every step in which any env needed tier 4 (configs[4]: 64 k ->
+// 42 k env-steps/s when tier 4 came in).  Envs that START in tier 4 (UHC_DEBUG bit 12) are put at the head of that queue by the list kernel.
+bool sticky_launch4(int last_tier, int est4, int est2_then, bool queues_off) { return last_tier == 4 && est4 > 0 && est2_then > 0 && !queues_off; }
+
+StickySizes plan_sticky_step(const StickyInputs& in, bool launch4) {
     StickySizes s;
     s.fast = plan_fast_chunks(in.n_substeps, in.n_substeps > 0 ? default_fast_chunk(in.fast_chunk, in.n_substeps, in.n_env, in.n_cu, in.lds_bytes_fast) : 0, in.n_env);
     const int est2 = in.est2, est3 = in.est3, est4 = in.est4, n_env = in.n_env, n_cu = in.n_cu;
     const bool big = in.last_tier >= 3;  // (tier 4 has no chained launch of its own: the large tier's workgroups go on with it; under sticky tiers it has queue consumers)
-    s.launch4 = in.last_tier == 4 && est4 > 0 && in.est2_then > 0 && big && !in.queues_off;  // (the list kernel's view; the consumers need the large tier's beside them: q4 below)
+    s.launch4 = launch4;  // (the list kernel's view; the consumers need the large tier's beside them: q4 below)
     // Three regimes.  No env in the general tier when last seen: no side launches, plain chain.  Up to three quarters of the batch
     // there: its launch is a CONSUMER that also waits for what the fast tier hands on while both run -- and is kept small enough that
     // the fast tier's workgroups always find LDS beside it (a consumer that holds all LDS while it waits for a launch that cannot
@@ -713,4 +720,49 @@ StickySizes plan_sticky_step(const StickyInputs& in) {
     //  them made its last workgroups start 25 ms into the step on the ball-joint rollout's first steps)
     s.n_wait = std::min(64, std::max(in.q2_wait_min, 2 * in.handed2 + 8));
     return s;
+}
+
+// Who waits for whom: tier 4's consumers for the large tier's exits, the large tier's for the general tier's, the general tier's -- while the fast tier still
+// has most of the envs (`waiting`) -- for the fast tier's; each tier hands on into the queue of the next one that has consumers this step.  A consumer of the
+// large tier or tier 4 that finds its queue empty always waits (n_wait = grid, no seat counter); of the general tier's only n_wait do, counted in UHC_FIN_SPARES.
+StepWiring sticky_wiring(const StickySizes& z, bool large_first) {
+    StepWiring w{};
+    auto add = [&](int tier, int stream, int grid) -> StepLaunch& {
+        StepLaunch& l = w.launch[w.n++];
+        l.tier = tier; l.stream = stream; l.grid = grid; l.prod_total = 0; l.n_wait = 0; l.gate_want = 0; l.tier_want = 0; l.chunk = 0; l.use_order = false;
+        l.list = l.count = l.cursor = l.spares = l.started = l.prod_fin = l.fin = l.next_list = l.next_count = l.gate_started = l.gate_waited = UHC_NONE;
+        return l;
+    };
+    if (z.q4) {  // (first of the side launches: a whole CU's LDS each, only to be had before the fast tier's launch has filled the chip)
+        StepLaunch& l = add(4, STREAM_T4, z.grid4);
+        l.list = UHC_LIST_T4; l.count = UHC_CNT_T4; l.cursor = UHC_CUR_T4; l.n_wait = z.grid4;
+        l.prod_fin = UHC_FIN_BIG; l.prod_total = z.grid3;
+    }
+    auto large = [&]() {
+        StepLaunch& l = add(3, STREAM_BIG, z.grid3);
+        l.list = UHC_LIST_BIG; l.count = UHC_CNT_BIG; l.cursor = UHC_CUR_BIG; l.n_wait = z.grid3; l.started = UHC_FIN_BIG_IN;
+        l.prod_fin = UHC_FIN_GEN; l.prod_total = z.grid2;  // the general tier's workgroups: they never wait for this launch
+        if (z.q4) { l.fin = UHC_FIN_BIG; l.next_list = UHC_LIST_T4; l.next_count = UHC_CNT_T4; }
+    };
+    // (the large tier's consumers first where their stream has a queue pool of its own: whole CUs are only free while nothing else is resident, so the general
+    //  tier's launch waits behind a gate until they have reported in)
+    if (z.q3 && large_first) large();
+    if (z.queues) {
+        StepLaunch& l = add(2, STREAM_GEN, z.grid2);
+        l.list = UHC_LIST_GEN; l.count = UHC_CNT_GEN; l.cursor = UHC_CUR_GEN; l.n_wait = z.n_wait; l.spares = UHC_FIN_SPARES; l.fin = UHC_FIN_GEN;
+        if (z.waiting) { l.started = UHC_FIN_GEN_IN; l.prod_fin = UHC_FIN_FAST; l.prod_total = z.fast.prod_total; }  // every workgroup of the fast tier's launch
+        if (z.q3) { l.next_list = UHC_LIST_BIG; l.next_count = UHC_CNT_BIG; }
+        if (z.q3 && large_first) { l.gate_started = UHC_FIN_BIG_IN; l.gate_want = z.grid3; }
+    }
+    if (z.q3 && !large_first) large();
+    // The fast tier's launch fills every CU's LDS the moment it starts; consumers that are not resident by then get theirs only when its first workgroups leave
+    // (the tier trace showed them starting 3.7 ms into the step).  A one-thread gate on its stream holds the launch back until every consumer workgroup has
+    // reported in (or 200 us have passed).
+    StepLaunch& f = add(1, STREAM_MAIN, z.fast.grid);  // (in substep chunks: n_chunks x n_env workgroups, chunk-major by ticket)
+    f.tier_want = 1; f.chunk = z.fast.chunk; f.use_order = true;  // (costliest envs first)
+    if (z.waiting) {
+        f.fin = UHC_FIN_FAST; f.next_list = UHC_LIST_GEN; f.next_count = UHC_CNT_GEN;
+        f.gate_started = UHC_FIN_GEN_IN; f.gate_want = z.grid2; f.gate_waited = UHC_CNT_GATE_WAIT;
+    }
+    return w;
 }

@@ -7,7 +7,7 @@
 #include "uhc_host.h"
 
 // the UHC_* environment variables of batch creation, parsed and range-checked (read_knobs is the one place of the host code that reads the environment)
-struct BatchKnobs {
+struct BatchKnobs : QueueCaps {    // (the caps: UHC_Q2_DIV, UHC_Q2_WAIT, UHC_Q2_MAX, UHC_Q3_MAX, UHC_Q4_MAX)
     int dbg = 0;                    // UHC_DEBUG (KernelArgs::dbg; bits 8-12 only in -DUHC_EXPERIMENTS builds)
     int marks[8] = {64, 16, -1, 56, 14, 10, 8, 7};  // UHC_TIER_MARKS "a,b,c,d,e,f,g,h" (marks[2] < 0: body-body marks follow the fast layout)
     int fast_dense_got = 0, fast_dense_kib = 0, fast_dense_rows = 0, fast_dense_con = 0;  // UHC_FAST_DENSE "KiB,dense rows[,contacts]": fields read, their values
@@ -17,7 +17,6 @@ struct BatchKnobs {
     bool force_general = false;     // UHC_FORCE_GENERAL=1
     int tiers = 0;                  // UHC_TIERS: 2, 3 or 0 (unset / anything else: four tiers)
     int guard = 0;                  // UHC_GUARD_LDS: 1 guard words, 2 the self-test (one guard ON qpos of the fast tier), 0 off
-    int q2_div = 1, q2_wait_min = 16, q2_max = 256, q3_max = 32, q4_max = 16;  // UHC_Q2_DIV >= 1, UHC_Q2_WAIT >= 1, UHC_Q2_MAX >= 16, UHC_Q3_MAX >= 2, UHC_Q4_MAX >= 0
     int t4_rows = 0;                // UHC_T4_ROWS >= 0
     int fast_chunk = 0;             // UHC_FAST_CHUNK=<substeps>: the fast tier's control step runs in chunks of so many substeps (0: not given, default_fast_chunk
                                     // decides; a value >= n_substeps, and "0" itself, mean one chunk: the whole-step launch)
@@ -45,7 +44,12 @@ struct BatchPlan {
 int plan_batch(const UhcModel* const* models, int n_models, const int32_t* env_model, int n_env, const UhcCtrlDesc* ctrl, const BatchKnobs& knobs,
                BatchPlan* out, std::string* err);
 
-// sticky tiers: the sizes of one step's consumer launches from the newest queue counts the host has seen (launch() in uhc_capi.cpp)
+// ------------------------------------------------------------------ sticky tiers: one step's launches from the newest queue counts the host has seen
+// (launch_sticky() in uhc_capi.cpp calls these three in turn: sticky_launch4, plan_sticky_step, sticky_wiring)
+
+// Do tier 4's queue consumers run this step?  The list kernel needs the answer at the head of the step (it fills their queue), before the host waits for
+// older counts and updates its back-off: queues_off here is the value the step BEGINS with.  est4, est2_then: as in StickyInputs
+bool sticky_launch4(int last_tier, int est4, int est2_then, bool queues_off);
 struct StickyInputs {
     int est2, est3, est4;  // queue lengths of the general / large tier at the end of the newest step seen; env-steps that went through tier 4
     int est2_then;         // the general tier's queue in the step est4 is from
@@ -55,7 +59,7 @@ struct StickyInputs {
     bool large_first;      // the large tier's consumers are launched before the general tier's
     int last_tier;
     bool queues_off;       // no waiting consumers (back-off after a consumer gave up)
-    int q2_div, q2_wait_min, q2_max, q3_max, q4_max;
+    int q2_div, q2_wait_min, q2_max, q3_max, q4_max;  // QueueCaps, member for member (set_caps): the test probes fill this struct by position AND set these by name
     bool fixed_cap2;       // measurement switch (UHC_DEBUG bit 11 of -DUHC_EXPERIMENTS builds): a fixed cap UHC_Q2_MAX on the general tier's consumers
     int fast_chunk;        // BatchKnobs::fast_chunk (0: the default), and the control step's substeps (0: the fast tier's launch is not chunked)
     int n_substeps;
@@ -72,8 +76,35 @@ void fast_chunk_range(const FastChunks& f, int n_substeps, int c, int* lo, int* 
 // the chunk size of a launch: the knob when given, else by whether the batch fills the chip's places for fast-tier workgroups more than once
 int default_fast_chunk(int knob, int n_substeps, int n_env, int n_cu, size_t lds_bytes_fast);
 struct StickySizes {
-    bool queues, waiting, q3, q4, launch4;
-    int grid2, grid3, grid4, n_wait, sticky_mask;
+    bool queues, waiting, q3, q4, launch4;  // consumers of the general tier / ... that wait for the fast tier's hand-ons / of the large tier / of tier 4; the launch4 given
+    int grid2, grid3, grid4, n_wait, sticky_mask;  // (sticky_mask: KernelArgs::sticky_mask of the step's side launches and of the fast tier's)
     FastChunks fast;
 };
-StickySizes plan_sticky_step(const StickyInputs& in);
+inline void set_caps(StickyInputs& in, const QueueCaps& c) { in.q2_div = c.q2_div; in.q2_wait_min = c.q2_wait_min; in.q2_max = c.q2_max; in.q3_max = c.q3_max; in.q4_max = c.q4_max; }
+// launch4: sticky_launch4 as the step's list kernel was told; the library calls this once per step.  The form without it is the step in which the back-off does
+// not flip -- in.queues_off decides both --, which is what the recorded sticky cases of tests/batch_plan_recording.json are
+StickySizes plan_sticky_step(const StickyInputs& in, bool launch4);
+inline StickySizes plan_sticky_step(const StickyInputs& in) { return plan_sticky_step(in, sticky_launch4(in.last_tier, in.est4, in.est2_then, in.queues_off)); }
+
+// The step's launches beside each other as a table: who consumes which queue, whose exits a consumer waits for, who hands on to whom, which gate holds which
+// launch back.  Slots are indices into the batch's lists / counts / cursors / fin (UhcList / UhcCount / UhcCursor / UhcFin, uhc_device.h); UHC_NONE: the launch
+// does not use the field (a null pointer or 0 in its KernelArgs).  The chained launches that follow on the batch's stream use none of this and are not listed.
+#define UHC_NONE (-1)
+enum StepStream { STREAM_MAIN = 0, STREAM_GEN = 1, STREAM_BIG = 2, STREAM_T4 = 3 };  // the batch's stream and the side streams of the general / large tier / tier 4
+struct StepLaunch {
+    int tier;                        // 4, 3, 2: queue consumers of that tier; 1: the fast tier's launch, one workgroup per (chunk, env)
+    int stream;                      // StepStream
+    int list, count, cursor;         // the queue this launch consumes
+    int grid;                        // workgroups
+    int n_wait, spares;              // so many workgroups that find the queue empty stay and wait; the counter of the seats taken (none: every one may wait)
+    int started;                     // bumped once per workgroup on entry
+    int prod_fin, prod_total;        // the queue's producers: it can grow until this counter has reached prod_total (none: it does not grow)
+    int fin;                         // bumped once per workgroup on exit
+    int next_list, next_count;       // where an env this tier cannot hold is handed on (none: it is flagged for the chained launches)
+    int gate_started, gate_want;     // a gate in front of the launch, on its stream: until so many workgroups have bumped that counter (none: no gate)
+    int gate_waited;                 // ... the count slot that receives the gate's wait
+    int tier_want, chunk;            // the fast tier's: KernelArgs::tier_want, substeps per chunk (0: the whole step)
+    bool use_order;                  // ... and it runs in the list kernel's launch order
+};
+struct StepWiring { int n; StepLaunch launch[4]; };  // in launch order: tier 4, then large before general exactly when large_first, the fast tier last
+StepWiring sticky_wiring(const StickySizes& z, bool large_first);
