@@ -48,13 +48,15 @@ __device__ __forceinline__ void rotT(double* r, const double* m, const double* v
     r[2] = m[2] * v[0] + m[5] * v[1] + m[8] * v[2];
 }
 __device__ __forceinline__ void heading_q(double* hq, const double* q) {  // math_utils.py:134-139
-    const double n = sqrt(q[0] * q[0] + q[3] * q[3]);
+    const double n = sqrt(fma(q[3], q[3], q[0] * q[0]));  // np.linalg.norm's order (see heading())
     hq[0] = q[0] / n; hq[1] = 0; hq[2] = 0; hq[3] = q[3] / n;
 }
 __device__ __forceinline__ double heading(const double* q) {  // math_utils.py:177-184
     double w = q[0], z = q[3];
     if (z < 0) { w = -w; z = -z; }
-    return 2 * acos(w / sqrt(w * w + z * z));
+    // the norm as np.linalg.norm accumulates it (w^2 rounded, z^2 fused onto it): next to yaw 0 acos turns one float64 step of the quotient
+    // into 2 / sqrt(1 - x^2) steps of the heading (4.4e-13 at yaw 1e-3), so the order of the two squares is visible in the observation
+    return 2 * acos(w / sqrt(fma(z, z, w * w)));
 }
 __device__ __forceinline__ double heading_new(const double* q) {  // math_utils.py:185-190
     return atan2(2 * (q[0] * q[3] + q[1] * q[2]), 1 - 2 * (q[2] * q[2] + q[3] * q[3]));
