@@ -151,6 +151,31 @@ enum UhcField {
     UHC_F_QACC_WARMSTART = 19, /* [n_env][nv] data.qacc_warmstart: what the next step's first solve starts from */
     UHC_F_COST = 20          /* int32 [n_env] how close the env's last step came to any capacity of the fast tier, in sixty-fourths: orders the fast tier's launch */
 };
+/* the bits of UHC_F_REDO (the prose above says what each means) */
+#define UHC_REDO_GENERAL (1 << 0)       /* computed by the general tier, the large one or tier 4 */
+#define UHC_REDO_SWEPT (1 << 1)         /* in at least one substep the solve fell back to sweeps */
+#define UHC_REDO_WHY_FRICTION (1 << 2)  /* ... why: friction-loss rows */
+#define UHC_REDO_WINDOWED (1 << 3)      /* an island was solved in windows of 64 rows (not a fallback) */
+#define UHC_REDO_WHY_NOCONV (1 << 4)    /* ... why: no convergence of the working sets */
+#define UHC_REDO_WHY_PIVOT (1 << 5)     /* ... why: a working set the pivoting could not solve */
+#define UHC_REDO_LARGE (1 << 6)         /* computed by the large tier or tier 4 */
+#define UHC_REDO_DROPPED (1 << 7)       /* rows / contacts beyond the last tier's capacity were dropped in this step */
+#define UHC_REDO_SWEPT_SUBSTEP0 (1 << 8) /* UHC_REDO_SWEPT_SUBSTEP0 << k: substep k was solved by sweeps, k < UHC_REDO_SWEPT_SUBSTEPS */
+#define UHC_REDO_SWEPT_SUBSTEPS 21
+#define UHC_REDO_PRIMAL_CAP (1 << 29)   /* a Newton iteration of tier 4 stopped at its cap */
+#define UHC_REDO_PRIMAL (1 << 30)       /* (part of) the step was solved by tier 4 */
+/* UHC_F_HANDON_WHY: four fields of UHC_HANDON_FIELD's width; the reason bits of the three tiers' fields */
+#define UHC_HANDON_FIELD 0xff
+#define UHC_HANDON_FAST_SHIFT 0         /* why the fast tier handed the env on */
+#define UHC_HANDON_GENERAL_SHIFT 8      /* why the general tier did */
+#define UHC_HANDON_SUBSTEP_SHIFT 16     /* the substep of the last hand-on */
+#define UHC_HANDON_LARGE_SHIFT 24       /* why the large tier handed the env on to tier 4 */
+#define UHC_HANDON_CONTACTS 1
+#define UHC_HANDON_ROWS 2
+#define UHC_HANDON_DENSE_SLOTS 4
+#define UHC_HANDON_ROW_STORAGE 8
+#define UHC_HANDON_CANDIDATES 16
+#define UHC_HANDON_SOLVER 32
 
 const char* uhc_last_error(void);
 int32_t uhc_abi_version(void);

@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from uhc_amd._capi import UhcCtrlDesc, UhcModelDesc, ctrl_desc, model_desc
+from uhc_amd._capi import REDO_SWEPT_SUBSTEP0, REDO_SWEPT_SUBSTEPS, UhcCtrlDesc, UhcModelDesc, ctrl_desc, model_desc
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
@@ -51,6 +51,11 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def swept_substeps(redo):
+    """The swept-substep field of a UHC_F_REDO word: bit k = the device solved substep k by sweeps (what orc_do_simulation_mixed takes)."""
+    return (int(redo) // REDO_SWEPT_SUBSTEP0) & ((1 << REDO_SWEPT_SUBSTEPS) - 1)
+
+
 class OracleSim:
     """One environment of the CPU oracle."""
 
@@ -82,11 +87,11 @@ class OracleSim:
         self.call("step")
 
     def do_simulation(self, action, target_base, redo=0):
-        """redo: the device path's UHC_F_REDO word of the same step; its bits 8+ name the substeps the device solved by sweeps after its
+        """redo: the device path's UHC_F_REDO word of the same step; its swept-substep bits (REDO_SWEPT_SUBSTEP0 << k) name the substeps the device solved by sweeps after its
         exact solve gave up, and the checker takes solver 0 in exactly those."""
         action = np.ascontiguousarray(action, dtype=np.float64)
         target_base = np.ascontiguousarray(target_base, dtype=np.float64)
-        self.L.orc_do_simulation_mixed(C.byref(self.desc), C.byref(self.ctrl), self.d, _dp(action), _dp(target_base), (int(redo) >> 8) & 0x1fffff)
+        self.L.orc_do_simulation_mixed(C.byref(self.desc), C.byref(self.ctrl), self.d, _dp(action), _dp(target_base), swept_substeps(redo))
 
     def pd_torque(self, action, target_base, it):
         action = np.ascontiguousarray(action, dtype=np.float64)

@@ -155,3 +155,41 @@ extern "C" __attribute__((visibility("default"))) long long uhc_plan_probe_table
 }
 extern "C" __attribute__((visibility("default"))) void uhc_plan_probe_sticky(const int* in17, int* out10) { run_sticky(in17, out10); }
 extern "C" __attribute__((visibility("default"))) void uhc_plan_probe_wiring(const int* in20, int* out95) { run_wiring(in20, out95); }
+
+// ---- the step's words and the tier policy (uhc_step_words.h) for tests/test_step_words_cpu.py, on the marks and capacities of the plan probed last
+// last_tier, t4_rows < 0: the plan's own
+static KernelArgs args_with(int last_tier, int t4_rows) {
+    KernelArgs A = g_plan.A;
+    if (last_tier >= 0) A.last_tier = last_tier;
+    if (t4_rows >= 0) A.t4_rows = t4_rows;
+    return A;
+}
+#define PROBE extern "C" __attribute__((visibility("default")))
+PROBE int uhc_sw_next_tier(int tier, const int* pk, int last_tier, int t4_rows, int sticky4) { return next_tier(tier, pk[0], pk[1], pk[2], pk[3], pk[4], args_with(last_tier, t4_rows), sticky4 != 0); }
+PROBE int uhc_sw_launch_cost(const int* pk, double vmax_end) { return launch_cost(pk[0], pk[1], pk[2], pk[3], vmax_end, g_plan.A); }
+PROBE int uhc_sw_redo_word(int tier, int status, int swept_mask) { return redo_word(tier, status, swept_mask); }
+PROBE int uhc_sw_redo_written(int tier, int status) { return redo_written(tier, status) ? 1 : 0; }
+PROBE int uhc_sw_swept_mask(int mask, int status, int it) { return redo_swept_mask(mask, status, it); }
+// (as k_forward puts them together; exact: solver 1, the sweeps are the fallback of the working sets)
+PROBE int uhc_sw_ws_gave_up_status(int exact, int code) { return UHC_ST_SWEPT | ((exact && code != UHC_WS_LOST) ? UHC_WS_REASON(code) : 0); }
+PROBE int uhc_sw_handon_why_word(int tier, int old_word, int status, int substep) { return handon_why_word(tier, old_word, status, substep); }
+PROBE int uhc_sw_order_bucket(int tier, int masked, int active, int fresh, int cost) { return order_bucket(&tier, masked != 0, &active, &fresh, &cost, 0); }
+// (as uhc_tier_lists_kernel puts the two rules together)
+PROBE int uhc_sw_start_tier(int tier, int fresh, int launch4) {
+    const int t = start_tier(tier, &fresh, 0);
+    return t == 4 ? start_tier4(launch4 != 0) : t;
+}
+// pk[5], *status: merged in place with the record rec[UHC_CHUNK_REC], word by word as uhc_step_env does
+PROBE void uhc_sw_chunk_rec_merge(int* pk, int* status, const int* rec) {
+    const int words[5] = {UHC_REC_PK_NEFC, UHC_REC_PK_NCON, UHC_REC_PK_NTWO, UHC_REC_PK_Y, UHC_REC_PK_ACT};
+    for (int k = 0; k < 5; k++) pk[k] = chunk_rec_merged(words[k], pk[k], rec[words[k]]);
+    *status = chunk_rec_merged(UHC_REC_STATUS, *status, rec[UHC_REC_STATUS]);
+}
+// the names the test needs by value: the status bits in UhcStatus's order, UHC_WHY_SHIFT, k_as_general's give-up codes, the record's words, UHC_ORDER_BUCKETS
+PROBE void uhc_sw_names(int* out) {
+    const int o[26] = {UHC_ST_HANDON, UHC_ST_DROPPED, UHC_ST_SWEPT, UHC_ST_WHY_FRICTION, UHC_ST_WINDOWED, UHC_ST_WHY_NOCONV, UHC_ST_WHY_PIVOT, UHC_ST_PRIMAL, UHC_ST_PRIMAL_CAP,
+                       UHC_WHY_SHIFT, UHC_WS_FRICTION, UHC_WS_LOST, UHC_WS_NOCONV, UHC_WS_PIVOT, UHC_WS_TIER4,
+                       UHC_REC_PK_NEFC, UHC_REC_PK_NCON, UHC_REC_PK_NTWO, UHC_REC_PK_Y, UHC_REC_PK_ACT, UHC_REC_NCON, UHC_REC_NEFC, UHC_REC_ITERS, UHC_REC_STATUS, UHC_CHUNK_REC,
+                       UHC_ORDER_BUCKETS};
+    memcpy(out, o, sizeof o);
+}

@@ -70,7 +70,7 @@ def build_probe():
     os.makedirs(out_dir, exist_ok=True)
     so = os.path.join(out_dir, "plan_probe.so")
     srcs = [os.path.join(ROOT, "tests", "plan_probe.cpp"), os.path.join(CSRC, "uhc_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("uhc_plan.h", "uhc_host.h", "uhc_device.h")] + [os.path.join(ROOT, "include", "uhc_amd.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("uhc_plan.h", "uhc_host.h", "uhc_device.h", "uhc_step_words.h")] + [os.path.join(ROOT, "include", "uhc_amd.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
         tmp = so + f".{os.getpid()}.tmp"

@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from uhc_amd.sim import REDO_SWEPT
+
 pytestmark = pytest.mark.gpu
 
 
@@ -66,7 +68,7 @@ def test_ball_humanoid_trajectory_matches_oracle(model, standing, kernel_path, l
     b.sync()
     os_ = [OracleSim(ball, ctrl) for _ in range(n)]
     for e in range(n):
-        os_[e].desc.solver = 0 if (int(b.field(S.F_REDO)[e].item()) & 2) else 1
+        os_[e].desc.solver = 0 if (int(b.field(S.F_REDO)[e].item()) & REDO_SWEPT) else 1
         os_[e].set_state(q[e], v[e])
         np.testing.assert_allclose(b.field(S.F_QM)[e].cpu().numpy(), os_[e].get("qM"), atol=1e-10)
         np.testing.assert_allclose(b.field(S.F_QACC)[e].cpu().numpy(), os_[e].get("qacc"), atol=1e-5, rtol=1e-6)
@@ -103,7 +105,7 @@ def test_ball_humanoid_with_objects_and_self_collision(model, standing, kernel_p
     os_ = [OracleSim(ball, ctrl) for _ in range(n)]
     redo = b.field(S.F_REDO).cpu().numpy()
     for e in range(n):
-        os_[e].desc.solver = 0 if (redo[e] & 2) else 1
+        os_[e].desc.solver = 0 if (redo[e] & REDO_SWEPT) else 1
         os_[e].set_state(q[e], v[e])
         assert int(b.field(S.F_NCON)[e].item()) == os_[e].geti("ncon") and int(b.field(S.F_NEFC)[e].item()) == os_[e].geti("nefc")
     for o in os_:
@@ -154,7 +156,7 @@ def test_ball_joint_limits_match_oracle(model, standing, kernel_path, self_colli
     os_ = [OracleSim(ball, ctrl) for _ in range(n)]
     redo = b.field(S.F_REDO).cpu().numpy()
     for e in range(n):
-        os_[e].desc.solver = 0 if (redo[e] & 2) else 1
+        os_[e].desc.solver = 0 if (redo[e] & REDO_SWEPT) else 1
         os_[e].set_state(q[e], v[e])
         assert int(b.field(S.F_NEFC)[e].item()) == os_[e].geti("nefc")
         np.testing.assert_allclose(b.field(S.F_QACC)[e].cpu().numpy(), os_[e].get("qacc"), atol=1e-5, rtol=1e-6)

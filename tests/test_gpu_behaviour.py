@@ -9,6 +9,7 @@ import pytest
 
 from tests.helpers import passive_ctrl
 from tests.test_oracle_physics import scenario_pushed_box, scenario_tilted_gravity_box
+from uhc_amd.sim import REDO_SWEPT
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +38,7 @@ def _run(models, q0s, v0s, n_steps, applied=None, settle=0):
         if applied is not None and t == settle:
             b.field(S.F_QFRC_APPLIED).copy_(torch.from_numpy(np.stack(applied)).cuda())
         b.simulate(act, act)
-        swept += ((b.field(S.F_REDO) & 2) != 0).long()  # steps whose exact solve gave up and swept to tolerance (general tier)
+        swept += ((b.field(S.F_REDO) & REDO_SWEPT) != 0).long()  # steps whose exact solve gave up and swept to tolerance (general tier)
     b.sync()
     b.swept_steps = swept.cpu().numpy()
     return b

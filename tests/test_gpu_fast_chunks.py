@@ -14,6 +14,8 @@ import os
 import numpy as np
 import pytest
 
+from uhc_amd.sim import REDO_GENERAL, WHY_FAST_SHIFT, WHY_FIELD, WHY_SUBSTEP_SHIFT
+
 pytestmark = pytest.mark.gpu
 
 CHUNKS = (1, 3, 5, 8)
@@ -82,7 +84,7 @@ def _rollout(ref, new, qpos, qvel, steps, ctrl, seed, tb, path, reset_every=7, a
             b.sync()
         _assert_same(ref, new, f"{where} step {t}")
         why, redo = new.field(S.F_HANDON_WHY).cpu().numpy(), new.field(S.F_REDO).cpu().numpy()
-        handed_mid += int((((redo & 1) != 0) & ((why & 0xff) != 0) & (((why >> 16) & 0xff) >= 1)).sum())
+        handed_mid += int((((redo & REDO_GENERAL) != 0) & (((why >> WHY_FAST_SHIFT) & WHY_FIELD) != 0) & (((why >> WHY_SUBSTEP_SHIFT) & WHY_FIELD) >= 1)).sum())
     assert int(new.field(S.F_FAIL).sum().item()) == int(ref.field(S.F_FAIL).sum().item())
     return handed_mid
 
@@ -151,7 +153,7 @@ def test_hand_on_from_a_later_chunk_is_bit_equal(model, standing, chunk, path):
             b.sync()
         _assert_same(ref, new, f"drop chunk {chunk} step {t}")
         why, redo = new.field(S.F_HANDON_WHY).cpu().numpy(), new.field(S.F_REDO).cpu().numpy()
-        later += int((((redo & 1) != 0) & ((why & 0xff) != 0) & (((why >> 16) & 0xff) >= chunk)).sum())
+        later += int((((redo & REDO_GENERAL) != 0) & (((why >> WHY_FAST_SHIFT) & WHY_FIELD) != 0) & (((why >> WHY_SUBSTEP_SHIFT) & WHY_FIELD) >= chunk)).sum())
     assert later >= 1, "no env was handed on from a chunk >= 1"
     _no_giveups(ref, new)
 

@@ -19,6 +19,8 @@ import os
 import numpy as np
 import pytest
 
+from uhc_amd.sim import REDO_DROPPED, REDO_GENERAL, REDO_LARGE, REDO_PRIMAL, REDO_PRIMAL_CAP, REDO_SWEPT, REDO_WINDOWED
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_STEPS = 200
@@ -159,12 +161,12 @@ def _run(name, model, standing, mode, handover, steps=N_STEPS, act_scale=None, s
                          o_fail=np.array([o.geti("fail") for o in os_])))
     # ---- the report: per env, when (if ever) it leaves the tolerance, and what the step before / at the exit looked like
     rep = dict(workload=name, mode=mode, handover=bool(handover), resync_every_step=bool(resync), steps=steps, action_scale=a_sc, worst=float(np.nanmax(err)),
-               env_steps_primal=int(sum(((i["redo"] & (1 << 30)) != 0).sum() for i in info)), env_steps_primal_cap=int(sum(((i["redo"] & (1 << 29)) != 0).sum() for i in info)),
+               env_steps_primal=int(sum(((i["redo"] & REDO_PRIMAL) != 0).sum() for i in info)), env_steps_primal_cap=int(sum(((i["redo"] & REDO_PRIMAL_CAP) != 0).sum() for i in info)),
                worst_first_50=float(np.nanmax(err[:50])), nefc_max=int(max(i["nefc"].max() for i in info)), ncon_max=int(max(i["ncon"].max() for i in info)),
-               env_steps_general_or_large=int(sum((i["redo"] & 1).sum() for i in info)), env_steps_large=int(sum(((i["redo"] & 0x40) != 0).sum() for i in info)),
-               env_steps_swept=int(sum(((i["redo"] & 2) != 0).sum() for i in info)), env_steps_windowed=int(sum(((i["redo"] & 8) != 0).sum() for i in info)),
-               env_steps_rows_dropped=int(sum(((i["redo"] & 0x80) != 0).sum() for i in info)), ties=ties, failed=failed,
-               env_steps_primal_by_rows=sorted(int(x) for i in info for x in i["nefc"][(i["redo"] & (1 << 30)) != 0])[-16:], leaves=[])
+               env_steps_general_or_large=int(sum((i["redo"] & REDO_GENERAL).sum() for i in info)), env_steps_large=int(sum(((i["redo"] & REDO_LARGE) != 0).sum() for i in info)),
+               env_steps_swept=int(sum(((i["redo"] & REDO_SWEPT) != 0).sum() for i in info)), env_steps_windowed=int(sum(((i["redo"] & REDO_WINDOWED) != 0).sum() for i in info)),
+               env_steps_rows_dropped=int(sum(((i["redo"] & REDO_DROPPED) != 0).sum() for i in info)), ties=ties, failed=failed,
+               env_steps_primal_by_rows=sorted(int(x) for i in info for x in i["nefc"][(i["redo"] & REDO_PRIMAL) != 0])[-16:], leaves=[])
     for e in range(n):
         bad = np.nonzero(~(err[:, e] < TOL))[0]
         if bad.size == 0:
@@ -172,9 +174,9 @@ def _run(name, model, standing, mode, handover, steps=N_STEPS, act_scale=None, s
         t = int(bad[0])
         before = [i for i in info[:t + 1]]
         why = []
-        if any((i["redo"][e] & 0x80) for i in before):
+        if any((i["redo"][e] & REDO_DROPPED) for i in before):
             why.append("rows dropped beyond the last tier's capacity in an earlier step")
-        if any((i["redo"][e] & 2) for i in before):
+        if any((i["redo"][e] & REDO_SWEPT) for i in before):
             why.append("an exact solve fell back to sweeps" + ("" if handover else " (nothing handed over: the oracle stayed exact)"))
         flips = [k for k, i in enumerate(before) if i["ncon"][e] != i["o_ncon"][e] or i["nefc"][e] != i["o_nefc"][e]]
         if flips:

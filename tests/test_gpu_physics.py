@@ -7,6 +7,8 @@ pytestmark = pytest.mark.gpu
 
 import os
 
+from uhc_amd.sim import REDO_GENERAL, REDO_SWEPT
+
 
 @pytest.fixture(params=["fast", "general"], autouse=True)
 def kernel_path(request):
@@ -432,8 +434,8 @@ def test_oracle_decides_its_own_solver(model, ctrl, standing, kernel_path):
         b.sync()
         gq, gv = b.field(S.F_QPOS).cpu().numpy(), b.field(S.F_QVEL).cpu().numpy()
         redo = b.field(S.F_REDO).cpu().numpy()
-        swept += int(((redo & 2) != 0).sum())
-        assert ((redo & 1) != 0).all() == (kernel_path == "general") or kernel_path == "fast"
+        swept += int(((redo & REDO_SWEPT) != 0).sum())
+        assert ((redo & REDO_GENERAL) != 0).all() == (kernel_path == "general") or kernel_path == "fast"
         for e in range(n):
             os_[e].do_simulation(act[e], qpos[e, 7:])  # no redo= : the checker's own decision
             worst = max(worst, np.abs(gq[e] - os_[e].get("qpos")).max(), np.abs(gv[e] - os_[e].get("qvel")).max())

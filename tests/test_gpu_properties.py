@@ -10,6 +10,8 @@ import dataclasses
 import numpy as np
 import pytest
 
+from uhc_amd.sim import REDO_GENERAL, REDO_SWEPT
+
 pytestmark = pytest.mark.gpu
 
 
@@ -118,13 +120,13 @@ def test_self_colliding_batch_does_not_depend_on_the_fast_tier_layout(model, ctr
     actions = np.random.default_rng(8).normal(scale=np.exp(-2.3), size=(steps, n_env, ctrl.action_dim))
     fields = dict(qpos=S.F_QPOS, qvel=S.F_QVEL, nefc=S.F_NEFC, fail=S.F_FAIL, redo=S.F_REDO, ov=S.F_EFC_OVERFLOW)
     full = _run(m, ctrl, qpos, qvel, actions, fields, steps)
-    assert not full["fail"].any() and not full["ov"].any() and not (full["redo"] & 2).any()
+    assert not full["fail"].any() and not full["ov"].any() and not (full["redo"] & REDO_SWEPT).any()
     again = _run(m, ctrl, qpos, qvel, actions, fields, steps)
     assert np.array_equal(full["qpos"], again["qpos"]) and np.array_equal(full["qvel"], again["qvel"])
     pick = np.random.default_rng(3).choice(n_env, 16, replace=False)
     small = _run(m, ctrl, qpos[pick], qvel[pick], np.ascontiguousarray(actions[:, pick]), fields, steps)
-    moved = int(((full["redo"][pick] & 1) != (small["redo"] & 1)).sum())
+    moved = int(((full["redo"][pick] & REDO_GENERAL) != (small["redo"] & REDO_GENERAL)).sum())
     dq, dv = np.abs(full["qpos"][pick] - small["qpos"]).max(), np.abs(full["qvel"][pick] - small["qvel"]).max()
-    print(f"3072-env batch vs 16-env batch: {moved} of 16 envs ended in another tier; |dqpos| {dq:.2e} |dqvel| {dv:.2e}; general-tier share of the big batch {(full['redo'] & 1).mean():.3f}")
+    print(f"3072-env batch vs 16-env batch: {moved} of 16 envs ended in another tier; |dqpos| {dq:.2e} |dqvel| {dv:.2e}; general-tier share of the big batch {(full['redo'] & REDO_GENERAL).mean():.3f}")
     assert np.array_equal(full["nefc"][pick], small["nefc"])
     assert dq < 1e-9 and dv < 1e-7, (dq, dv)

@@ -3,6 +3,8 @@ and against the reference's row-by-row Welford filter; then a whole sampling pas
 import numpy as np
 import pytest
 
+from uhc_amd.sim import REDO_DROPPED, REDO_GENERAL, REDO_LARGE, REDO_PRIMAL, REDO_PRIMAL_CAP, REDO_SWEPT, REDO_WINDOWED
+
 pytestmark = pytest.mark.gpu
 
 
@@ -105,8 +107,8 @@ def test_act_and_record_equal_the_framework_expressions():
     redo = torch.tensor([0, 1, 3, 0x70b, 0x80, 0xc1, 0x40000041, 0x60000041] * (n_env // 8) + [1] * (n_env % 8), dtype=torch.int32, device=dev)
     rc = torch.tensor([10, 20, 30, 40, 50, 60, 70], dtype=torch.long, device=dev)
     ops.record(t, reward, done, end, er, parts, 5, rewards, dones, crs, cis, redo, rc)
-    assert rc.tolist() == [10 + int(((redo & 1) != 0).sum()), 20 + int(((redo & 2) != 0).sum()), 30 + int(((redo & 0x80) != 0).sum()), 40 + int(((redo & 0x40) != 0).sum()), 50 + int(((redo & 8) != 0).sum()),
-                           60 + int(((redo & (1 << 30)) != 0).sum()), 70 + int(((redo & (1 << 29)) != 0).sum())]  # (tier 4: solved by Newton on the primal; its iteration cap)
+    assert rc.tolist() == [10 + int(((redo & REDO_GENERAL) != 0).sum()), 20 + int(((redo & REDO_SWEPT) != 0).sum()), 30 + int(((redo & REDO_DROPPED) != 0).sum()), 40 + int(((redo & REDO_LARGE) != 0).sum()), 50 + int(((redo & REDO_WINDOWED) != 0).sum()),
+                           60 + int(((redo & REDO_PRIMAL) != 0).sum()), 70 + int(((redo & REDO_PRIMAL_CAP) != 0).sum())]  # (tier 4: solved by Newton on the primal; its iteration cap)
     assert torch.equal(rewards[:, 3], reward + end.double() * 2.5) and torch.equal(dones[:, 3], done.double())
     np.testing.assert_allclose(float(crs), 1.0 + float(reward.sum()), rtol=1e-14)
     np.testing.assert_allclose(cis.cpu().numpy(), 1.0 + parts[:, :5].sum(0).cpu().numpy(), rtol=1e-14)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import box_triangles, passive_ctrl
+from uhc_amd.sim import REDO_SWEPT
 
 pytestmark = pytest.mark.gpu
 
@@ -117,7 +118,7 @@ def test_rounded_hull_contacts_match_oracle(kernel_path):
     plane_round = round_mesh = round_round = 0
     for e in range(n):
         o = OracleSim(m)
-        o.desc.solver = 0 if (int(b.field(S.F_REDO)[e].item()) & 2) else 1
+        o.desc.solver = 0 if (int(b.field(S.F_REDO)[e].item()) & REDO_SWEPT) else 1
         o.set_state(q[e], v[e])
         assert ncon[e] == o.geti("ncon") and nefc[e] == o.geti("nefc"), (e, ncon[e], o.geti("ncon"), nefc[e], o.geti("nefc"))
         np.testing.assert_allclose(qacc[e], o.get("qacc"), atol=1e-6 * (1 + np.abs(o.get("qacc")).max()), rtol=1e-6)
@@ -163,7 +164,7 @@ def test_rounded_hull_trajectories_match_oracle(kernel_path):
         redo = b.field(S.F_REDO).cpu().numpy()
         for e in range(n):
             o = os_[e]
-            o.desc.solver = 0 if (int(redo[e]) & 2) else 1
+            o.desc.solver = 0 if (int(redo[e]) & REDO_SWEPT) else 1
             o.set_state(pq[e], pv[e])
             o.do_simulation(za, zt)
             err = max(np.abs(gq[e] - o.get("qpos")).max(), np.abs(gv[e] - o.get("qvel")).max())

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import passive_ctrl, two_box_model
+from uhc_amd.sim import REDO_DROPPED, REDO_GENERAL, REDO_LARGE, REDO_PRIMAL, REDO_PRIMAL_CAP, REDO_SWEPT, REDO_WINDOWED
 
 pytestmark = pytest.mark.gpu
 
@@ -55,7 +56,7 @@ def test_mpr_contacts_match_oracle(kernel_path):
     hits = 0
     for e in range(n):
         o = OracleSim(m)
-        o.desc.solver = 0 if (int(b.field(S.F_REDO)[e].item()) & 2) else 1
+        o.desc.solver = 0 if (int(b.field(S.F_REDO)[e].item()) & REDO_SWEPT) else 1
         o.set_state(q[e], v[e])
         assert ncon[e] == o.geti("ncon") and nefc[e] == o.geti("nefc"), e
         np.testing.assert_allclose(qacc[e], o.get("qacc"), atol=1e-6, rtol=1e-6)
@@ -118,7 +119,7 @@ def test_self_collision_humanoid_matches_oracle(model, standing, kernel_path, li
     ncon, nefc, qacc, redo = (b.field(f).cpu().numpy() for f in (S.F_NCON, S.F_NEFC, S.F_QACC, S.F_REDO))
     nself = 0
     for e in range(n):
-        os_[e].desc.solver = 0 if (redo[e] & 2) else 1
+        os_[e].desc.solver = 0 if (redo[e] & REDO_SWEPT) else 1
         os_[e].set_state(qpos[e], qvel[e])
         assert ncon[e] == os_[e].geti("ncon") and nefc[e] == os_[e].geti("nefc"), (e, ncon[e], os_[e].geti("ncon"))
         np.testing.assert_allclose(qacc[e], os_[e].get("qacc"), atol=1e-5, rtol=1e-6)
@@ -254,7 +255,7 @@ def test_hand_on_resumes_at_the_substep(model, standing):
             bb.sync()
         redo, gq = resume.field(S.F_REDO).cpu().numpy(), resume.field(S.F_QPOS).cpu().numpy()
         tr = resume.field(S.F_STAGE_PROF).cpu().numpy()
-        substeps.append(np.where((redo & 1) != 0, tr[:, 6], -1))  # word 6 of the trace: the substep the fast tier handed the env on in
+        substeps.append(np.where((redo & REDO_GENERAL) != 0, tr[:, 6], -1))  # word 6 of the trace: the substep the fast tier handed the env on in
         apart = max(apart, np.abs(gq - restart.field(S.F_QPOS).cpu().numpy()).max())
         for e in range(n):
             os_[e].do_simulation(act[e], qpos[e, 7:], redo=redo[e])
@@ -299,7 +300,7 @@ def test_lying_humanoid_among_boxes_exceeds_128_rows(model, standing):
     os_ = [OracleSim(m, ctrl) for _ in range(n)]
     redo = b.field(S.F_REDO).cpu().numpy()
     for e in range(n):
-        os_[e].desc.solver = 0 if (redo[e] & 2) else 1
+        os_[e].desc.solver = 0 if (redo[e] & REDO_SWEPT) else 1
         os_[e].set_state(q[e], v[e])
         os_[e].desc.solver = 1
     tb = torch.zeros(n, 69, dtype=torch.float64, device="cuda")
@@ -315,7 +316,7 @@ def test_lying_humanoid_among_boxes_exceeds_128_rows(model, standing):
             os_[e].do_simulation(act[e], np.zeros(69), redo=redo[e])
             assert nefc[e] == os_[e].geti("nefc"), (t, e, nefc[e], os_[e].geti("nefc"))
             worst = max(worst, np.abs(gq[e] - os_[e].get("qpos")).max())
-            big_steps += int((redo[e] & 0x40) != 0)
+            big_steps += int((redo[e] & REDO_LARGE) != 0)
             max_nefc = max(max_nefc, os_[e].geti("max_nefc"))
     print(f"lying humanoid + 4 boxes: max nefc {max_nefc}, env-steps in the large tier {big_steps} / {12 * n}, worst |dqpos| {worst:.2e}")
     assert max_nefc > 128 and big_steps > 0
@@ -370,10 +371,10 @@ def test_island_with_more_than_64_force_rows_is_solved_exactly(model, standing, 
         gq, gv = b.field(S.F_QPOS).cpu().numpy(), b.field(S.F_QVEL).cpu().numpy()
         redo = b.field(S.F_REDO).cpu().numpy()
         for e in range(n):
-            windowed += int((redo[e] & 8) != 0)
-            primal += int((redo[e] & (1 << 30)) != 0)
-            assert not (redo[e] & (1 << 29)), hex(int(redo[e]))  # (the Newton iteration never ran into its cap)
-            swept += int((redo[e] & 2) != 0)
+            windowed += int((redo[e] & REDO_WINDOWED) != 0)
+            primal += int((redo[e] & REDO_PRIMAL) != 0)
+            assert not (redo[e] & REDO_PRIMAL_CAP), hex(int(redo[e]))  # (the Newton iteration never ran into its cap)
+            swept += int((redo[e] & REDO_SWEPT) != 0)
             os_[e].set_state(gq0[e], gv0[e])
             os_[e].do_simulation(act[e], np.zeros(69))
             dq, dv = np.abs(gq[e] - os_[e].get("qpos")).max(), np.abs(gv[e] - os_[e].get("qvel")).max()
@@ -432,11 +433,11 @@ def test_pass_that_drops_rows_is_flagged_and_bounded(model, standing, monkeypatc
         redo = b.field(S.F_REDO).cpu().numpy()
         nefc_max = max(nefc_max, int(b.field(S.F_NEFC).max().item()))
         for e in range(n):
-            if redo[e] & 0x80:
+            if redo[e] & REDO_DROPPED:
                 lost_steps += 1
                 words.append(hex(int(redo[e])))
-                assert redo[e] & 0x40, hex(int(redo[e]))  # in the large tier
-                swept += int((redo[e] & 2) != 0)
+                assert redo[e] & REDO_LARGE, hex(int(redo[e]))  # in the large tier
+                swept += int((redo[e] & REDO_SWEPT) != 0)
     print(f"humanoid face down + raft of {K} boxes: {lost_steps} of {4 * n} env-steps lost rows beyond 256 (nefc at the steps' ends up to {nefc_max}), {swept} of them ended a substep in the short sweeps; UHC_F_REDO of those: {words[:4]}")
     assert lost_steps > 0  # (UHC_F_NEFC is the step's LAST substep: the rows were lost in its first ones)
     assert int(b.field(S.F_EFC_OVERFLOW).sum().item()) > 0 and int(b.field(S.F_FAIL).sum().item()) == 0
@@ -496,8 +497,8 @@ def test_more_rows_than_the_dual_tiers_hold_are_solved_by_tier_4(model, standing
             gq, gv = b.field(S.F_QPOS).cpu().numpy(), b.field(S.F_QVEL).cpu().numpy()
             redo = b.field(S.F_REDO).cpu().numpy()
             for e in range(n):
-                assert not (redo[e] & 0x80) and not (redo[e] & 2) and not (redo[e] & (1 << 29)), (t, e, hex(int(redo[e])))
-                primal += int((redo[e] & (1 << 30)) != 0)
+                assert not (redo[e] & REDO_DROPPED) and not (redo[e] & REDO_SWEPT) and not (redo[e] & REDO_PRIMAL_CAP), (t, e, hex(int(redo[e])))
+                primal += int((redo[e] & REDO_PRIMAL) != 0)
                 os_[e].set_state(gq0[e], gv0[e])
                 os_[e].do_simulation(act[e], np.zeros(69))
                 worst_q = max(worst_q, np.abs(gq[e] - os_[e].get("qpos")).max())
@@ -564,8 +565,8 @@ def test_sticky_queues_hand_an_env_on_to_tier_4(model, standing):
             os_[e].set_state(q[e], v[e])
             os_[e].do_simulation(act[e], np.zeros(69))
             worst = max(worst, np.abs(gq[e] - os_[e].get("qpos")).max())
-            primal += int((redo[e] & (1 << 30)) != 0)
-        assert not (redo & 0x80).any() and not (redo & 2).any(), [hex(int(x)) for x in redo]
+            primal += int((redo[e] & REDO_PRIMAL) != 0)
+        assert not (redo & REDO_DROPPED).any() and not (redo & REDO_SWEPT).any(), [hex(int(x)) for x in redo]
     print(f"sticky queues + tier 4: env-steps through tier 4 {primal} / {6 * n}; next-step tiers {tiers.tolist()}; worst |dqpos| {worst:.2e}")
     assert primal >= 6 and worst < 1e-9, (primal, worst)
     assert int(b.field(S.F_EFC_OVERFLOW).sum().item()) == 0 and int(b.field(S.F_FAIL).sum().item()) == 0
@@ -626,9 +627,9 @@ def test_tier_4_consumers_take_what_the_large_tiers_consumers_hand_on(model, sta
             os_[e].set_state(q[e], v[e])
             os_[e].do_simulation(act[e], np.zeros(69))
             worst = max(worst, np.abs(gq[e] - os_[e].get("qpos")).max())
-            primal += int((redo[e] & (1 << 30)) != 0)
-            assert bool(redo[e] & (1 << 30)) == (e in heavy), (t, e, hex(int(redo[e])))
-        assert not (redo & 0x80).any() and not (redo & 2).any(), [hex(int(x)) for x in redo]
+            primal += int((redo[e] & REDO_PRIMAL) != 0)
+            assert bool(redo[e] & REDO_PRIMAL) == (e in heavy), (t, e, hex(int(redo[e])))
+        assert not (redo & REDO_DROPPED).any() and not (redo & REDO_SWEPT).any(), [hex(int(x)) for x in redo]
     err = capfd.readouterr().err
     launched = [ln for ln in err.splitlines() if "tier-4 consumers" in ln]
     print(f"all queues + tier 4's consumers: {len(launched)} of 8 steps had them ({launched[:1]}); env-steps through tier 4 {primal}; next-step tiers {tiers_seen[-1]}; worst |dqpos| {worst:.2e}")
@@ -682,7 +683,7 @@ def test_a_dof_chain_of_32_entries_goes_through_tier_4(monkeypatch, capfd):
         b.simulate(torch.from_numpy(act).cuda(), tb)
         b.sync()
         redo = b.field(S.F_REDO).cpu().numpy()
-        assert ((redo >> 30) & 1).all() and not (redo & 0x80).any() and not (redo & 2).any() and not ((redo >> 29) & 1).any(), [hex(int(x)) for x in redo]
+        assert ((redo & REDO_PRIMAL) != 0).all() and not (redo & REDO_DROPPED).any() and not (redo & REDO_SWEPT).any() and not (redo & REDO_PRIMAL_CAP).any(), [hex(int(x)) for x in redo]
         for e in range(n):
             os_[e].do_simulation(act[e], np.zeros(max(m.nu, 1)))
             worst = max(worst, np.abs(b.field(S.F_QPOS)[e].cpu().numpy() - os_[e].get("qpos")).max(), np.abs(b.field(S.F_QVEL)[e].cpu().numpy() - os_[e].get("qvel")).max())
@@ -704,13 +705,13 @@ def test_a_dof_chain_of_32_entries_goes_through_tier_4(monkeypatch, capfd):
         b.simulate(torch.from_numpy(act).cuda(), tb)
         b.sync()
         redo = b.field(S.F_REDO).cpu().numpy()
-        assert not (redo & 0x80).any() and not (redo & 2).any() and not ((redo >> 29) & 1).any(), [hex(int(x)) for x in redo]
+        assert not (redo & REDO_DROPPED).any() and not (redo & REDO_SWEPT).any() and not (redo & REDO_PRIMAL_CAP).any(), [hex(int(x)) for x in redo]
         for e in range(n):
             os_[e].set_state(q[e], v[e])
             os_[e].do_simulation(act[e], np.zeros(max(m.nu, 1)))
             worst2 = max(worst2, np.abs(b.field(S.F_QPOS)[e].cpu().numpy() - os_[e].get("qpos")).max())
-            primal += int((redo[e] >> 30) & 1)
-            assert bool((redo[e] >> 30) & 1) == (e in flat), (t, e, hex(int(redo[e])), int(b.field(S.F_NEFC)[e].item()))
+            primal += int((redo[e] & REDO_PRIMAL) != 0)
+            assert bool(redo[e] & REDO_PRIMAL) == (e in flat), (t, e, hex(int(redo[e])), int(b.field(S.F_NEFC)[e].item()))
     err = capfd.readouterr().err
     launched = [ln for ln in err.splitlines() if "tier-4 consumers" in ln]
     print(f"32-entry dof chains: chained launches worst {worst:.2e}; sticky queues: {len(launched)} of 8 steps with tier-4 consumers, {primal} env-steps through tier 4, worst |dqpos| {worst2:.2e}")

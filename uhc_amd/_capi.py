@@ -6,6 +6,13 @@ from typing import List
 
 import numpy as np
 
+# the bits of UHC_F_REDO and the fields of UHC_F_HANDON_WHY: the header's UHC_REDO_* / UHC_HANDON_* (tests/test_step_words_cpu.py compares the two; uhc_amd.sim re-exports them)
+REDO_GENERAL, REDO_SWEPT, REDO_WHY_FRICTION, REDO_WINDOWED, REDO_WHY_NOCONV, REDO_WHY_PIVOT, REDO_LARGE, REDO_DROPPED = (1 << k for k in range(8))
+REDO_SWEPT_SUBSTEP0, REDO_SWEPT_SUBSTEPS = 1 << 8, 21  # REDO_SWEPT_SUBSTEP0 << k: substep k < REDO_SWEPT_SUBSTEPS was solved by sweeps
+REDO_PRIMAL_CAP, REDO_PRIMAL = 1 << 29, 1 << 30
+WHY_FIELD, WHY_FAST_SHIFT, WHY_GENERAL_SHIFT, WHY_SUBSTEP_SHIFT, WHY_LARGE_SHIFT = 0xff, 0, 8, 16, 24
+WHY_CONTACTS, WHY_ROWS, WHY_DENSE_SLOTS, WHY_ROW_STORAGE, WHY_CANDIDATES, WHY_SOLVER = (1 << k for k in range(6))
+
 _I32P = C.POINTER(C.c_int32)
 _F64P = C.POINTER(C.c_double)
 

@@ -51,7 +51,6 @@ extern "C" hipError_t uhc_launch_set_state(const DevState* s, int nq, int nv, in
 // sticky tiers, head of a control step: snapshot of the tier table + the queues of the general / large tier, which start with the active
 // envs that begin the step there (lists UHC_LIST_GEN, UHC_LIST_BIG of n_env slots each, free slots = -1; counts UHC_CNT_GEN, UHC_CNT_BIG),
 // the cursors the persistent launches share and the counters their workgroups bump (UhcFin).  The words' names: uhc_device.h
-#define UHC_ORDER_BUCKETS 9
 // (tier 4, `launch4` != 0: tier 4's queue consumers run this step; the envs whose last step ended in tier 4 (UHC_DEBUG bit 12 only) head their queue -- list UHC_LIST_T4,
 //  count UHC_CNT_T4 -- and are flagged pend3 = 2, "straight to tier 4"; with launch4 == 0 they are the large tier's like any tier-3 env and the snapshot says 3)
 __global__ void uhc_tier_lists_kernel(const int* tier, const int* d_active, int n_env, int* tier_now, int* lists, int* counts, int* cursors, int* fin,
@@ -68,28 +67,19 @@ __global__ void uhc_tier_lists_kernel(const int* tier, const int* d_active, int 
     // capacity, which is also what its step time grows with), then the envs that are not this launch's.  The launch does not fit the chip
     // at once; whatever starts in its second round is then cheap and far from the capacity -- the envs that may still be handed on are
     // handed on EARLY, while the consumers of the next tier have time left, and the launch's last workgroups are its shortest.
-    auto bucket = [&](int env) {
-        if (tier[env] != 1 || (d_active && !d_active[env])) return UHC_ORDER_BUCKETS;
-        // (an env restarted since its last step has no history: its reset pose may not fit the tier at all -- many do not -- and it is handed
-        //  on in its first forward pass; at the head of the launch that happens while the next tier's consumers still have the step ahead)
-        if (fresh[env]) return 0;  // (a bucket of their own, ahead of everything: with the row storage in the cost, the next bucket holds hundreds of envs)
-        // (round 6: the cost counts the packed row storage too, which on the ball-joint / object models puts most envs within an eighth of the capacity:
-        //  the scale is fine where the hand-ons are -- an env that no longer fits in its first forward pass must not start in the launch's last round)
-        const int c = cost[env];  // 0 .. 64+ (sixty-fourths of the capacity)
-        return c >= 62 ? 1 : c >= 59 ? 2 : c >= 56 ? 3 : c >= 52 ? 4 : c >= 48 ? 5 : c >= 40 ? 6 : c >= 24 ? 7 : 8;
-    };
+    // (the buckets and the tier an env starts in: order_bucket, start_tier -- uhc_step_words.h)
     for (int env = threadIdx.x; env < n_env; env += blockDim.x) {
-        int t = tier[env];
+        const int was = tier[env];
         const bool on = !d_active || d_active[env];
-        if (t == 4 && fresh[env]) t = 2;  // (a restarted env has no history: its reset pose is the general tier's to look at, not a whole CU's)
+        int t = start_tier(was, fresh, env);
         if (t == 4) {
             if (on) atomicAdd(&counts[UHC_CNT_T4_STEPS], 1);  // (the step's tier-4 envs: these and every hand-on to tier 4, KernelArgs::cnt4)
-            if (launch4 && on) { lists[UHC_LIST_T4 * n_env + atomicAdd(&counts[UHC_CNT_T4], 1)] = env; pend3[env] = 2; }
-            else if (!launch4) t = 3;
+            if (launch4 && on) { lists[UHC_LIST_T4 * n_env + atomicAdd(&counts[UHC_CNT_T4], 1)] = env; pend3[env] = 2; }  // flagged "straight to tier 4"
+            else t = start_tier4(launch4 != 0);
         }
         tier_now[env] = t;
         if ((t == 2 || t == 3) && on) lists[(UHC_LIST_GEN + t - 2) * n_env + atomicAdd(&counts[UHC_CNT_GEN + t - 2], 1)] = env;
-        if (order) atomicAdd(&nb[bucket(env)], 1);
+        if (order) atomicAdd(&nb[order_bucket(tier, d_active != nullptr, d_active, fresh, cost, env)], 1);
     }
     __syncthreads();
     if (threadIdx.x < 2) counts[UHC_CNT_GEN_HEAD + threadIdx.x] = counts[UHC_CNT_GEN + threadIdx.x];  // the queues as the step begins (the host compares with how they end)
@@ -99,7 +89,7 @@ __global__ void uhc_tier_lists_kernel(const int* tier, const int* d_active, int 
         for (int k = 0; k <= UHC_ORDER_BUCKETS; k++) { const int c = nb[k]; nb[k] = run; run += c; }
     }
     __syncthreads();
-    for (int env = threadIdx.x; env < n_env; env += blockDim.x) order[atomicAdd(&nb[bucket(env)], 1)] = env;
+    for (int env = threadIdx.x; env < n_env; env += blockDim.x) order[atomicAdd(&nb[order_bucket(tier, d_active != nullptr, d_active, fresh, cost, env)], 1)] = env;
 }
 extern "C" hipError_t uhc_launch_tier_lists(const int* tier, const int* d_active, int n_env, int* tier_now, int* lists, int* counts, int* cursors, int* fin,
                                             const int* cost, const int* fresh, int* order, int launch4, int* pend3, hipStream_t stream) {

@@ -29,13 +29,6 @@
 #define UHC_HUGE_MAXTWO 128
 #define UHC_DOF_MAXACT 4
 #define UHC_CON_STRIDE 24
-// why a tier could not hold an env (bits 16+ of the forward pass's overflow word; UHC_F_HANDON_WHY = the word >> 16 of the env's last hand-on)
-#define UHC_WHY_CONTACTS (1 << 16)
-#define UHC_WHY_ROWS (1 << 17)
-#define UHC_WHY_DENSE_SLOTS (1 << 18)
-#define UHC_WHY_ROW_STORAGE (1 << 19)
-#define UHC_WHY_CANDIDATES (1 << 20)
-#define UHC_WHY_SOLVER (1 << 21)  // the working sets of the general / large tier did not finish (more than 64 force-carrying rows in an island, no convergence): Newton on the primal takes over
 #define UHC_MINVAL 1e-15
 #define UHC_MAXVAL 1e10
 #define UHC_NPROF 40  // int64 words per env of the stage-profile record (UHC_F_STAGE_PROF)
@@ -141,8 +134,8 @@ struct DevState {  // HBM, env-major
     double *cdof, *rootcom;  // explicit RFC only: kinematics of the last forward pass carried between launches
     int *ncon, *nefc, *fail, *solver_iter, *overflow, *redo;
     int *pend2, *pend3;  // envs handed on to the general / large tier this step and not yet taken (the chained launches' active masks)
-    int* why;            // diagnostic (UHC_F_HANDON_WHY): bits 0-7 why the fast tier handed the env on in this step, bits 8-15 why the general tier did
-                         // (1 contacts, 2 rows, 4 body-body row slots, 8 packed row storage, 16 MPR candidate list), bits 16+ the substep of the last hand-on
+    int* why;            // diagnostic (UHC_F_HANDON_WHY): why the fast / general / large tier handed the env on in this step, and the substep of the last
+                         // hand-on (handon_why_word, uhc_step_words.h; the fields and reason bits: UHC_HANDON_*, include/uhc_amd.h)
     int* resume;         // substep at which the tier below handed the env on (its state then is in qpos / qvel / qacc_ws / ctrl / applied); 0: from the start
     int* q_abort;  // [0] consumers that gave up waiting for producers of which none had finished (queue_claim: the host backs off), and chunk waiters; [1] consumers that left behind producers that were running but slow (reported, not acted on)
     int* tier;   // per env: the tier that computed its last control step (minus hysteresis): where its next step starts (kernel path 2)
@@ -223,7 +216,7 @@ struct KernelArgs {
     int* guard_hits;       // ... [0] guard words found overwritten, [1] the first one: tier << 16 | kind << 8 | index, [2] its env, [3] its offset
     int* cnt4;            // sticky tiers: bumped once per env the large tier hands on to tier 4 (the host sizes the tier-4 consumers of the next steps by it), or NULL
     int grid;  // workgroups of a list launch (0: one per env)
-    int marks[8];  // sticky tiers: when an env starts its next step a tier up / down (uhc_step_env; UHC_TIER_MARKS)
+    int marks[8];  // sticky tiers: when an env starts its next step a tier up / down (UhcMark, next_tier: uhc_step_words.h; UHC_TIER_MARKS)
     int t4_rows;   // sticky tiers: an env of the general / large tier whose step peaked at this many rows or more starts its NEXT step in tier 4, at the head of the
                    // four-wave consumers' queue, and stays there while it peaks above 3/4 of the mark (0: never; UHC_T4_ROWS)
     int truncate;  // fast kernel: drop contacts / rows beyond its capacity instead of handing the env to the general kernel
@@ -246,5 +239,4 @@ struct KernelArgs {
 #define UHC_CHUNK_TAKEN (1 << 29)
 #define UHC_CHUNK_CLOSING (1 << 28)
 #define UHC_CHUNK_REC 16
-// chunk_rec words: 0-4 the peaks of the step's substeps so far (rows, contacts, body-body rows, packed Yhat entries, force-carrying rows: they decide the env's
-// next tier and its place in the launch order), 5-7 ncon / nefc / solver_iter of its newest forward pass, 8 the truncation bits
+// (the record's words: UhcChunkRecWord, uhc_step_words.h)

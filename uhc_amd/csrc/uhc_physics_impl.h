@@ -13,6 +13,7 @@
 #include <type_traits>
 #include "../../include/uhc_amd.h"
 #include "uhc_device.h"
+#include "uhc_step_words.h"
 
 extern __shared__ __attribute__((aligned(16))) double smem[];
 
@@ -984,7 +985,7 @@ __device__ __forceinline__ int k_collision(const KernelArgs& A, const double* mb
                 k_write_contact<TIER>(A, mb, S, ncon + rank, P.g1, P.g2, P.b1, P.b2, P.dim & 255, cp, n, dist, margin, gap, capsule ? cax : nullptr);
             }
             const int want = ncon + min((int)__popcll(cm), T.plane_mesh_maxcon);
-            if (want > cap_of<TIER>(A).maxcon) *overflow |= (hands_on<TIER>(A) ? 1 : 2) | UHC_WHY_CONTACTS;  // 1: needs the next tier, 2: dropped
+            if (want > cap_of<TIER>(A).maxcon) *overflow |= (hands_on<TIER>(A) ? UHC_ST_HANDON : UHC_ST_DROPPED) | UHC_WHY_CONTACTS;  // needs the next tier, or dropped
             ncon = min(cap_of<TIER>(A).maxcon, want);
         }
     }
@@ -1041,7 +1042,7 @@ __device__ __forceinline__ int k_collision(const KernelArgs& A, const double* mb
             if (c && rank < CAND_CAP) cand[rank] = p;
             ncand += (int)__popcll(cm);
         }
-        if (ncand > CAND_CAP) { *overflow |= (hands_on<TIER>(A) ? 1 : 2) | UHC_WHY_CANDIDATES; ncand = CAND_CAP; }
+        if (ncand > CAND_CAP) { *overflow |= (hands_on<TIER>(A) ? UHC_ST_HANDON : UHC_ST_DROPPED) | UHC_WHY_CANDIDATES; ncand = CAND_CAP; }
         PROF(33)
         // the hull vertices (body frame, model constants) into the LDS region the constraint rows will use after this pass
         const int vstage = cap_of<TIER>(A).vstage;
@@ -1092,7 +1093,7 @@ __device__ __forceinline__ int k_collision(const KernelArgs& A, const double* mb
                 k_write_contact<TIER>(A, mb, S, ncon + rank, g1, g2, M.b1, M.b2, max(T.geom_condim[g1], T.geom_condim[g2]), cp, nn, margin - M.depth, margin, gap);
             }
             const int want = ncon + (int)__popcll(hm);
-            if (want > cap_of<TIER>(A).maxcon) *overflow |= (hands_on<TIER>(A) ? 1 : 2) | UHC_WHY_CONTACTS;
+            if (want > cap_of<TIER>(A).maxcon) *overflow |= (hands_on<TIER>(A) ? UHC_ST_HANDON : UHC_ST_DROPPED) | UHC_WHY_CONTACTS;
             ncon = min(cap_of<TIER>(A).maxcon, want);
         }
         PROF(35)
@@ -1175,9 +1176,9 @@ __device__ __forceinline__ int k_enumerate_rows(const KernelArgs& A, const doubl
     }
     wsync();
     nefc = ((int*)(S + L.ncon_nefc))[1];
-    if (((int*)(S + L.ncon_nefc))[0]) *overflow |= 2;
-    if (((int*)(S + L.ncon_nefc))[3]) *overflow |= (hands_on<TIER>(A) ? 1 : 2) | UHC_WHY_DENSE_SLOTS;  // the next tier has more dense slots; the last one dropped the rows
-    if (nefc > cap_of<TIER>(A).maxefc) { *overflow |= (hands_on<TIER>(A) ? 1 : 2) | UHC_WHY_ROWS; nefc = cap_of<TIER>(A).maxefc; }
+    if (((int*)(S + L.ncon_nefc))[0]) *overflow |= UHC_ST_DROPPED;
+    if (((int*)(S + L.ncon_nefc))[3]) *overflow |= (hands_on<TIER>(A) ? UHC_ST_HANDON : UHC_ST_DROPPED) | UHC_WHY_DENSE_SLOTS;  // the next tier has more dense slots; the last one dropped the rows
+    if (nefc > cap_of<TIER>(A).maxefc) { *overflow |= (hands_on<TIER>(A) ? UHC_ST_HANDON : UHC_ST_DROPPED) | UHC_WHY_ROWS; nefc = cap_of<TIER>(A).maxefc; }
     return nefc;
 }
 
@@ -1569,7 +1570,7 @@ __device__ __forceinline__ int k_pgs(const KernelArgs& A, const double* mb, doub
 struct FastRow { int type, last, len, yoff, two /* dense slot or -1 */; double R, b, f, floss, diag; };
 
 
-// returns 0 on success, 1 if the packed Yhat rows do not fit (-> the env is redone by the general kernel)
+// returns 0 on success, UHC_ST_HANDON if the packed Yhat rows do not fit (-> the env is redone by the general kernel), UHC_ST_DROPPED if rows were dropped (truncate mode)
 // The row's Yhat = D^-1/2 L^-T J^T entries along its dof chain are built in REGISTERS (Y[q], q = position on the chain,
 // compile-time indices): Jacobian, the three J.v products, the back substitution and the D^-1/2 scaling never round-trip
 // through LDS (a lane-serial read-modify-write chain through LDS costs ~100 cycles per update with one wave per SIMD).
@@ -1599,7 +1600,7 @@ __device__ __forceinline__ int k_rows_fast(const KernelArgs& A, const double* mb
     *ytot = total;
     row.R = 1; row.b = 0; row.f = 0; row.floss = 0; row.diag = 1;
     if (total + 8 > A.cf.ycap) {
-        if (!A.truncate) return 1;
+        if (!A.truncate) return UHC_ST_HANDON;
         // keep the leading rows whose packed entries fit, cut back to the start of a pyramid so its edges stay together
         const unsigned long long fit = __builtin_amdgcn_ballot_w64(valid && row.yoff + row.len + 8 <= A.cf.ycap);
         int nfit = ~fit == 0ull ? UHC_WAVE : __ffsll((long long)~fit) - 1;
@@ -1609,10 +1610,10 @@ __device__ __forceinline__ int k_rows_fast(const KernelArgs& A, const double* mb
             nfit = upto ? 63 - __builtin_clzll(upto) : 0;
         }
         nefc = nfit;
-        status = 2;
+        status = UHC_ST_DROPPED;
         valid = r < nefc;
         if (!valid) { rm.type = 0; row.type = 0; row.len = 0; }
-        if (nefc == 0) return 2;
+        if (nefc == 0) return UHC_ST_DROPPED;
     }
     const int len = row.len;
     int maxlen = len;  // wave maximum (uniform)
@@ -2170,7 +2171,7 @@ __device__ __forceinline__ int k_as_general(const KernelArgs& A, const double* m
         vv[h] = rr[h] < nefc;
         fric = fric || (vv[h] && RTYPE(RM[rr[h]].type) == ROW_FRICTION);
     }
-    if (wave_or(fric)) return -1;
+    if (wave_or(fric)) return UHC_WS_FRICTION;
     // (D jar of every row, k_rows: how close the warm-start acceleration leaves it to carrying a force -- read before `list` / `label` reuse the storage)
     double pr[NRL];
 #pragma unroll
@@ -2295,8 +2296,8 @@ __device__ __forceinline__ int k_as_general(const KernelArgs& A, const double* m
 #pragma unroll
                 for (int h = 0; h < NRL; h++) { q[h] = __builtin_amdgcn_ballot_w64(c[h] && !p[h]); nq += __builtin_popcountll(q[h]); }
                 const int room = UHC_WAVE - (nC - nq);
-                if (room <= 0 && lost) return -2;  // (a pass that dropped rows is not worth the windows: k_forward)
-                if (room <= 0 && A.last_tier == 4) return -5;  // (an island with more force-carrying rows than lanes: Newton on the primal takes it, tier 4)
+                if (room <= 0 && lost) return UHC_WS_LOST;  // (a pass that dropped rows is not worth the windows: k_forward)
+                if (room <= 0 && A.last_tier == 4) return UHC_WS_TIER4;  // (an island with more force-carrying rows than lanes: Newton on the primal takes it, tier 4)
                 if (room <= 0 || block) {
                     // 64 rows carry a force and more want in: the next window of 64 candidates, cyclically from the cursor
                     if (!block) {
@@ -2433,7 +2434,7 @@ __device__ __forceinline__ int k_as_general(const KernelArgs& A, const double* m
             }
             PROF(30)
             const int it = k_pgs_fast<TIER, DENSE>(A, mb, S, nC, row, Y, LC, SLg, nslot PROF_PASS);  // exact on C (or its sweeps to tolerance); z = sum_C f Yhat
-            if (it < 0) return -4;  // pivot breakdown / no convergence of the pivoting on this working set
+            if (it < 0) return UHC_WS_PIVOT;  // pivot breakdown / no convergence of the pivoting on this working set
             iters += it > 0 ? it : 1;
             if (block) {  // z of the whole island
                 for (int i = LANE; i < T.nv; i += UHC_WAVE) z[i] += zfix[i];
@@ -2478,7 +2479,7 @@ __device__ __forceinline__ int k_as_general(const KernelArgs& A, const double* m
             }
         }
         if (split) { todo |= G; nomerge = true; continue; }
-        if (!done) return -3;
+        if (!done) return UHC_WS_NOCONV;
     }
     for (int i = LANE; i < T.nv; i += UHC_WAVE) z[i] = ztot[i];
     wsync();
@@ -2494,7 +2495,7 @@ __device__ __forceinline__ int k_primal(const KernelArgs& A, const double* mb, d
 #endif
 
 // ------------------------------------------------------------------ mj_forward
-struct FwdOut { int ncon, nefc, iters, overflow, nact, ytot; };  // ytot (fast tier): packed Yhat entries the pass's rows take  // nact (tier 4): rows that carry a force at the optimum  // overflow bit 0: the env does not fit this tier => redone by the next one
+struct FwdOut { int ncon, nefc, iters, overflow, nact, ytot; };  // ytot (fast tier): packed Yhat entries the pass's rows take  // nact (tier 4): rows that carry a force at the optimum  // overflow: the pass's status word, UhcStatus | UHC_WHY_* (uhc_step_words.h); UHC_ST_HANDON: the env does not fit this tier => redone by the next one
 // LDS guard words (debug builds, -DUHC_GUARD_LDS on top of -DUHC_POISON_LDS; the host lays them out with UHC_GUARD_LDS=1 -- uhc_capi.cpp): two doubles after
 // every region, holding the poison pattern; kind 0 = after the persistent regions (poisoned once per env with the rest of the LDS), kind 1 = after the
 // regions of the constraint phase (armed when the dynamics temporaries that overlay them are dead, checked when the forward pass returns)
@@ -2548,14 +2549,14 @@ __device__ __forceinline__ FwdOut k_forward(const KernelArgs& A, const double* m
     PROF(8)
     out.nefc = k_enumerate_rows<TIER, DENSE>(A, mb, S, out.ncon, &out.overflow);
     DofVec x = {0.0, 0.0};
-    if (out.overflow & 1) return out;  // (bit 0 is only raised by a tier that hands the env on)
+    if (out.overflow & UHC_ST_HANDON) return out;  // (only raised by a tier that hands the env on)
     if (out.nefc > 0) {
         if constexpr (TIER == 1) {
             FastRow row;
             double Yreg[UHC_YM];
-            const int st = k_rows_fast<DENSE>(A, mb, S, out.nefc, row, Yreg, LC, &out.ytot);  // 1: needs the general kernel, 2: rows dropped (truncate mode)
-            out.overflow |= st | (st == 1 ? UHC_WHY_ROW_STORAGE : 0);
-            if (st == 1) return out;
+            const int st = k_rows_fast<DENSE>(A, mb, S, out.nefc, row, Yreg, LC, &out.ytot);  // UHC_ST_HANDON: needs the general kernel, UHC_ST_DROPPED: rows dropped (truncate mode)
+            out.overflow |= st | (st == UHC_ST_HANDON ? UHC_WHY_ROW_STORAGE : 0);
+            if (st == UHC_ST_HANDON) return out;
             PROF(9)
             const int* NI = (const int*)(S + L.ncon_nefc);
             out.iters = k_pgs_fast<1, DENSE>(A, mb, S, out.nefc, row, Yreg, LC, NI + 4, DENSE ? NI[2] : 0 PROF_PASS);
@@ -2563,7 +2564,7 @@ __device__ __forceinline__ FwdOut k_forward(const KernelArgs& A, const double* m
         } else {
             double* Yb = y_store<TIER>(A, S, env);
             double* Db = d_store<TIER>(A, S, env);
-            if (k_rows<TIER>(A, mb, S, out.nefc, LC, Yb, Db)) { out.overflow |= 1 | UHC_WHY_ROW_STORAGE; return out; }  // the packed rows need the next tier's storage
+            if (k_rows<TIER>(A, mb, S, out.nefc, LC, Yb, Db)) { out.overflow |= UHC_ST_HANDON | UHC_WHY_ROW_STORAGE; return out; }  // the packed rows need the next tier's storage
             PROF(9)
             int it = -1;
             if constexpr (TIER == 4) {
@@ -2574,16 +2575,16 @@ __device__ __forceinline__ FwdOut k_forward(const KernelArgs& A, const double* m
                 fric = wave_or(fric);
                 if (T.solver == 1 && !fric) {
                     it = k_primal<TIER>(A, mb, S, out.nefc, LC, Yb, Db, &out.nact PROF_PASS);
-                    out.overflow |= 128;                            // UHC_F_REDO bit 30: solved by Newton on the primal
-                    if (it < 0) { out.overflow |= 256; it = -it; }  // bit 29: it stopped at its iteration cap (the best iterate is used)
+                    out.overflow |= UHC_ST_PRIMAL;                  // solved by Newton on the primal
+                    if (it < 0) { out.overflow |= UHC_ST_PRIMAL_CAP; it = -it; }  // it stopped at its iteration cap (the best iterate is used)
                 } else {
-                    if (T.solver == 1) out.overflow |= 4 | 8;
+                    if (T.solver == 1) out.overflow |= UHC_ST_SWEPT | UHC_ST_WHY_FRICTION;
                     it = k_pgs<TIER>(A, mb, S, out.nefc, T.iterations, Yb, Db);
                 }
                 out.iters = it;
                 PROF(11)
             } else {
-            // An env that has just lost rows or contacts beyond the last tier's capacity (overflow bit 1; UHC_F_REDO bit 7) is no longer
+            // An env that has just lost rows or contacts beyond the last tier's capacity (UHC_ST_DROPPED; UHC_REDO_DROPPED) is no longer
             // solving the reference's QP.  Most such passes are ordinary pile-ups and their truncated QP is solved exactly like any other.
             // One in twelve is a simulation on its way to the bad-value flag (tools/diag_redo.py on the configs[4] probe, replayed on
             // the checker: joint speeds of 160 - 20 000 rad/s at the head of the step, |b| of 1e7 - 5e16 in the substep, one island of 250
@@ -2591,13 +2592,13 @@ __device__ __forceinline__ FwdOut k_forward(const KernelArgs& A, const double* m
             // third of that probe's time.  A pass that has dropped rows therefore gets a bounded attempt -- UHC_WS_LOST_MAXIT working-set
             // rounds, no windows -- and, when that gives up, UHC_LOST_SWEEPS sweeps from the warm start.  (Batches whose last tier is the
             // large one, UHC_TIERS=3: with tier 4 behind it the large tier hands such an env on instead.)
-            const bool lost = T.solver == 1 && (out.overflow & 2) != 0;
+            const bool lost = T.solver == 1 && (out.overflow & UHC_ST_DROPPED) != 0;
             if (T.solver == 1) it = k_as_general<TIER, DENSE>(A, mb, S, out.nefc, LC, lost PROF_PASS);
-            if (it >= 0 && (it & UHC_WS_WINDOWED)) { it &= UHC_WS_WINDOWED - 1; out.overflow |= 16; }  // (UHC_F_REDO bit 3: an island was solved in windows)
-            if (it < -1 && T.solver == 1 && A.last_tier == 4) {
+            if (it >= 0 && (it & UHC_WS_WINDOWED)) { it &= UHC_WS_WINDOWED - 1; out.overflow |= UHC_ST_WINDOWED; }  // (an island was solved in windows)
+            if (it < UHC_WS_FRICTION && T.solver == 1 && A.last_tier == 4) {
                 // the working sets did not finish (an island with more force-carrying rows than lanes, no convergence, a pivot breakdown): the env
                 // goes on to tier 4, whose Newton iteration on the primal has no such limit -- instead of the sweeps of rounds 2-4
-                out.overflow |= 1 | UHC_WHY_SOLVER;
+                out.overflow |= UHC_ST_HANDON | UHC_WHY_SOLVER;
                 return out;
             }
             if (it < 0) {
@@ -2605,9 +2606,9 @@ __device__ __forceinline__ FwdOut k_forward(const KernelArgs& A, const double* m
                     for (int r = LANE; r < out.nefc; r += UHC_WAVE) S[L.rowF + r] = S[L.rowW + r];
                     wsync();
                 }
-                out.overflow |= 4 | ((T.solver == 1 && it != -2) ? (4 << (-it)) : 0);  // (-2: a pass that dropped rows met an island that needs windows)
+                out.overflow |= UHC_ST_SWEPT | ((T.solver == 1 && it != UHC_WS_LOST) ? UHC_WS_REASON(it) : 0);  // (UHC_WS_LOST: a pass that dropped rows met an island that needs windows)
                 it = k_pgs<TIER>(A, mb, S, out.nefc, lost ? min(T.iterations, UHC_LOST_SWEEPS) : T.iterations, Yb, Db);
-            }  // 4: solved by sweeps (to tolerance), reported in UHC_F_REDO bit 1; 8 / 32 / 64: why the working sets gave up (bits 2, 4, 5); 16: not a fallback (above)
+            }
             out.iters = it;
             PROF(11)
             }
@@ -2906,7 +2907,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
     wsync();
     FwdOut fo = {0, 0, 0, 0, 0, 0};
     int it = 0;
-    int overflow = 0, swept = 0;  // swept: bit 8 + k = substep k of this step was solved by the sweeps (general kernel, solver 1)
+    int overflow = 0, swept = 0;  // overflow: the status words of the step's forward passes (UhcStatus)  // swept: UHC_F_REDO's bits of the substeps that were solved by the sweeps (general kernel, solver 1)
     bool ran = false, fits = true;  // (ran: a forward pass ran in THIS invocation; a later chunk of a step also has those of the earlier chunks behind it: ran_step below)
     // fits (general / large tier): every substep of this step was within the fast kernel's capacity
     int pk_nefc = 0, pk_ncon = 0, pk_ntwo = 0, pk_y = 0, pk_act = 0;
@@ -2965,8 +2966,8 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
             guard_check<TIER>(A, S, env, 1);
             PROF(13)
             overflow |= fo.overflow;
-            if (overflow & 1) break;
-            if (TIER != 1 && (fo.overflow & 4) && it >= 0 && it < 21) swept |= 1 << (8 + it);  // (bits 8 .. 28; 29 and 30 report the primal solver)
+            if (overflow & UHC_ST_HANDON) break;
+            if (TIER != 1) swept = redo_swept_mask(swept, fo.overflow, it);
             if (TIER != 1) fits = fits && fo.nefc <= UHC_WAVE && fo.ncon <= A.cf.maxcon &&
                               (!(DENSE && cap_of<TIER>(A).ndense > 0) || ((const int*)(S + L.ncon_nefc))[2] <= A.cf.ndense);
             {
@@ -2995,7 +2996,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
             }
         }
     }
-    if (overflow & 1) {  // nothing committed: the next tier takes the env over -- from the substep that did not fit, or from the same inputs
+    if (overflow & UHC_ST_HANDON) {  // nothing committed: the next tier takes the env over -- from the substep that did not fit, or from the same inputs
         if (MODE == 0 && it >= 1 && it > res && !(A.dbg & 4)) {  // (UHC_DEBUG bit 2: hand on from the start of the step, for A/B measurements)
             for (int i = LANE; i < T.nq; i += UHC_WAVE) A.s.qpos[(size_t)env * T.nq + i] = S[L.qpos + i];
             for (int i = LANE; i < T.nv; i += UHC_WAVE) {
@@ -3014,8 +3015,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
             // (the large tier hands on to tier 4: pend3 = 2 -- in a one-workgroup-per-env launch the same workgroup goes on with it at once; a queue
             //  consumer leaves the env flagged for the step's chained large-tier launch, which takes a `2` straight to tier 4)
             if (TIER == 1) A.s.pend2[env] = 1; else if (TIER == 2) { A.s.pend2[env] = 0; A.s.pend3[env] = 1; } else A.s.pend3[env] = 2;
-            if (TIER <= 2) A.s.why[env] = (A.s.why[env] & (TIER == 1 ? 0xff00 : 0x00ff)) | (((overflow >> 16) & 0xff) << (TIER == 1 ? 0 : 8)) | ((it & 0xff) << 16);  // diagnostic: why, and at which substep
-            else A.s.why[env] |= ((overflow >> 16) & 0xff) << 24;  // bits 24+: why the large tier handed the env on to tier 4
+            A.s.why[env] = handon_why_word(TIER, A.s.why[env], overflow, it);  // diagnostic: why, and at which substep
             __threadfence();
             if (TIER == 3 && A.cnt4) atomicAdd(A.cnt4, 1);
             if (A.q_next) {  // the next tier's consumers are running beside this launch: straight into their queue
@@ -3069,14 +3069,16 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
         if (LANE < UHC_NPROF) A.s.prof[(size_t)env * UHC_NPROF + LANE] += mine;
     }
 #endif
+    // the record of the step's earlier chunks merged into the peaks and the status (words another workgroup wrote during this launch: read past the scalar cache, like `resume`)
+#define MERGE_WORD(rec, w, mine) mine = chunk_rec_merged(w, mine, chunk_rec_load(rec + w));
+#define MERGE_EARLIER_CHUNKS(rec) { MERGE_WORD(rec, UHC_REC_PK_NEFC, pk_nefc) MERGE_WORD(rec, UHC_REC_PK_NCON, pk_ncon) MERGE_WORD(rec, UHC_REC_PK_NTWO, pk_ntwo) MERGE_WORD(rec, UHC_REC_PK_Y, pk_y) \
+                                    MERGE_WORD(rec, UHC_REC_PK_ACT, pk_act) MERGE_WORD(rec, UHC_REC_STATUS, overflow) }
     if (CH && !fail && it_end < A.c.n_substeps) {  // the end of a chunk, not of the step: the next chunk's workgroup goes on from the state just stored
         if (LANE == 0) {  // the record: peaks and truncation bits merged with the earlier chunks', the counts of the newest forward pass (this chunk's)
             int* rec = A.chunk_rec + (size_t)env * UHC_CHUNK_REC;
-            if (lo > 0) {  // (words another workgroup wrote during this launch: read past the scalar cache, like `resume`)
-                pk_nefc = max(pk_nefc, chunk_rec_load(rec + 0)); pk_ncon = max(pk_ncon, chunk_rec_load(rec + 1)); pk_ntwo = max(pk_ntwo, chunk_rec_load(rec + 2));
-                pk_y = max(pk_y, chunk_rec_load(rec + 3)); pk_act = max(pk_act, chunk_rec_load(rec + 4)); overflow |= chunk_rec_load(rec + 8);
-            }
-            rec[0] = pk_nefc; rec[1] = pk_ncon; rec[2] = pk_ntwo; rec[3] = pk_y; rec[4] = pk_act; rec[5] = fo.ncon; rec[6] = fo.nefc; rec[7] = fo.iters; rec[8] = overflow;
+            if (lo > 0) MERGE_EARLIER_CHUNKS(rec)
+            rec[UHC_REC_PK_NEFC] = pk_nefc; rec[UHC_REC_PK_NCON] = pk_ncon; rec[UHC_REC_PK_NTWO] = pk_ntwo; rec[UHC_REC_PK_Y] = pk_y; rec[UHC_REC_PK_ACT] = pk_act;
+            rec[UHC_REC_NCON] = fo.ncon; rec[UHC_REC_NEFC] = fo.nefc; rec[UHC_REC_ITERS] = fo.iters; rec[UHC_REC_STATUS] = overflow;
         }
         return 2;
     }
@@ -3089,65 +3091,28 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
     if (LANE == 0) {
         if (CH && lo > 0) {  // the step's earlier chunks (their record, read past the scalar cache)
             const int* rec = A.chunk_rec + (size_t)env * UHC_CHUNK_REC;
-            pk_nefc = max(pk_nefc, chunk_rec_load(rec + 0)); pk_ncon = max(pk_ncon, chunk_rec_load(rec + 1)); pk_ntwo = max(pk_ntwo, chunk_rec_load(rec + 2));
-            pk_y = max(pk_y, chunk_rec_load(rec + 3)); pk_act = max(pk_act, chunk_rec_load(rec + 4)); overflow |= chunk_rec_load(rec + 8);
-            if (!ran) { fo.ncon = chunk_rec_load(rec + 5); fo.nefc = chunk_rec_load(rec + 6); fo.iters = chunk_rec_load(rec + 7); }  // (a bad value at the head of the chunk's first substep)
+            MERGE_EARLIER_CHUNKS(rec)
+            if (!ran) { fo.ncon = chunk_rec_load(rec + UHC_REC_NCON); fo.nefc = chunk_rec_load(rec + UHC_REC_NEFC); fo.iters = chunk_rec_load(rec + UHC_REC_ITERS); }  // (a bad value at the head of the chunk's first substep)
         }
         if (ran_step) { A.s.ncon[env] = fo.ncon; A.s.nefc[env] = fo.nefc; A.s.solver_iter[env] = fo.iters; }
         A.s.fail[env] = fail;
-        if (overflow & 3) A.s.overflow[env] = 1;
+        if (overflow & (UHC_ST_HANDON | UHC_ST_DROPPED)) A.s.overflow[env] = 1;
         A.s.fresh[env] = 0;
         if (TIER == 2) A.s.pend2[env] = 0;  // taken: the chained launch of this tier has nothing left to do for the env
         if (TIER >= 3) A.s.pend3[env] = 0;
-        // where the env's next step starts (uhc_batch_set_kernel_path 2): an env comes down a tier only with room to spare
-        // An env that comes CLOSE to a tier's capacity starts its next step one tier up: finding out in the middle of a step that it no
-        // longer fits costs that tier's work so far, and the step then ends a whole general- (or large-) tier env-step after the moment
-        // of the hand-on -- with a thousand envs some env does that every step, and every step lasts fast + general + large.  It comes
-        // down again only well below the mark (hysteresis).  The marks are the batch's (KernelArgs::marks, UHC_TIER_MARKS).
-        if (MODE == 0 && ran_step) {
-            const int* mk = A.marks;  // up2: rows, contacts, body-body rows | dn1: the same | up3, dn2: eighths of the general tier's capacities
-            const bool up2 = pk_nefc > mk[0] || pk_ncon > mk[1] || pk_ntwo > mk[2];   // of 64 rows / 16 contacts / 12 body-body rows
-            // (... and only if its packed rows fit the fast tier's storage: with objects in the model that storage is small, and an env that
-            //  fits by rows and contacts alone came down every step only to be handed on in its first forward pass)
-            const bool dn1 = pk_nefc <= mk[3] && pk_ncon <= mk[4] && pk_ntwo <= mk[5] && (TIER == 1 || pk_y + 8 <= (7 * A.cf.ycap) / 8);
-            const bool up3 = pk_nefc > (mk[6] * A.cg.maxefc) / 8 || pk_ncon > (mk[6] * A.cg.maxcon) / 8 || pk_ntwo > (mk[6] * A.cg.ndense) / 8 || pk_y > (mk[6] * A.cg.ycap) / 8;
-            const bool dn2 = pk_nefc <= (mk[7] * A.cg.maxefc) / 8 && pk_ncon <= (mk[7] * A.cg.maxcon) / 8 && pk_ntwo <= (mk[7] * A.cg.ndense) / 8 && pk_y <= (mk[7] * A.cg.ycap) / 8;
-            const int big = A.last_tier >= 3 ? 3 : 2;
-            int next;
-            if (TIER == 1) next = up2 ? 2 : 1;
-            else if (TIER == 2) next = (up3 && big == 3) ? 3 : (dn1 ? 1 : 2);
-            else next = !dn2 ? 3 : (dn1 ? 1 : 2);
-            // an env that needed tier 4 (beyond the large tier's capacities, or more force-carrying rows than its working sets finish) starts its next
-            // step THERE: at the head of the queue of tier 4's consumers (uhc_capi.cpp) instead of an abandoned large-tier attempt first.  It comes down with room to spare: 3/4 of the large tier's capacities and <= 48 rows with a force.
-            // OPT-IN (UHC_DEBUG bit 12): measured on the random-policy ball-joint rollouts it LOSES -- configs[4] 41.6 k -> 27.1 k env-steps/s: the envs that
-            // reach tier 4 there are diverging ones that reset within two or three steps, a reset env then runs its first step in tier 4 too, and a whole step of
-            // primal solves costs more than the large-tier attempt it saves -- so by default such an env starts its next step in the large tier.
-            // Heavy envs go STRAIGHT to tier 4 (round 6): the four-wave Newton iteration on the primal costs the same whatever the number of rows, while a
-            // general- or large-tier env-step grows with every working-set round -- and the step's slowest env is what a control step waits for.  An env
-            // whose step peaked at KernelArgs::t4_rows rows or more starts its next step at the head of tier 4's queue and stays while it peaks above 3/4 of that.
-            if (A.last_tier == 4 && A.t4_rows > 0 && ((TIER == 2 || TIER == 3) ? pk_nefc >= A.t4_rows : (TIER == 4 && 4 * pk_nefc >= 3 * A.t4_rows))) next = 4;
-            // (Sending SLOW envs there too -- by the duration of their last general-tier step -- was built and measured in round 6 and is gone again: a tier-4 env-step of a
-            //  60-80-row env is no shorter than its general-tier one, and a whole CU per env is what the fast tier's second round needs: profiles/r06_q_t4ticks_sweep.txt.)
-            if (TIER == 4 && UHC_EXP(4096) && A.last_tier == 4 && !(pk_nefc <= (3 * A.ch.maxefc) / 4 && pk_ncon <= (3 * A.ch.maxcon) / 4 && pk_ntwo <= (3 * A.ch.ndense) / 4 && pk_act <= 48)) next = 4;
-            A.s.tier[env] = next;
-            // the fast tier's launch order (uhc_tier_lists_kernel): how close the step came to ANY of the fast tier's capacities, in sixty-fourths -- rows, contacts,
-            // body-body rows and (round 6) the packed row storage, which names 2 of 3 hand-ons of the ball-joint rollouts (tools/tier_trace.py) -- and at the top of
-            // the scale an env whose joints spin faster than any tracked motion's: a simulation on its way to the bad-value flag piles up rows within a few
-            // substeps, goes through every tier and ends the step if it starts in the launch's last round (profiles/r06_b_tier_trace_configs4.txt)
-            int cost = max(pk_nefc, max((pk_ncon * UHC_FAST_MAXEFC) / max(A.cf.maxcon, 1), (pk_ntwo * UHC_FAST_MAXEFC) / max(A.cf.ndense, 1)));
-            cost = max(cost, (int)(((long long)pk_y * UHC_FAST_MAXEFC) / max(A.cf.ycap, 1)));
-            if (vmax_end > 60.0) cost = max(cost, UHC_FAST_MAXEFC); else if (vmax_end > 30.0) cost = max(cost, 40);
-            A.s.cost[env] = cost;
+        if (MODE == 0 && ran_step) {  // where the env's next step starts, and where in the fast tier's launch order (the policy: uhc_step_words.h)
+            A.s.tier[env] = next_tier(TIER, pk_nefc, pk_ncon, pk_ntwo, pk_y, pk_act, A, UHC_EXP(4096));
+            A.s.cost[env] = launch_cost(pk_nefc, pk_ncon, pk_ntwo, pk_y, vmax_end, A);
         }
-        if (TIER != 1) A.s.redo[env] = 1 | ((overflow & 4) ? 2 : 0) | ((overflow >> 1) & 0x3c) | (TIER >= 3 ? 0x40 : 0) | ((overflow & 2) ? 0x80 : 0) | swept |
-                                       ((overflow & 128) ? (1 << 30) : 0) | ((overflow & 256) ? (1 << 29) : 0);
-        else if (overflow & 2) A.s.redo[env] = 0x80;  // (fast tier in truncate mode; bit 7 = rows / contacts were dropped in this step)
+        if (redo_written(TIER, overflow)) A.s.redo[env] = redo_word(TIER, overflow, swept);
         if (TIER != 1 && MODE == 0) {
             atomicAdd(A.s.path_stats + 2, 1ull);
             if (fits) atomicAdd(A.s.path_stats + 1, 1ull);
-        }  // UHC_F_REDO: bit 0 = computed by the general kernel, bit 1 = its contact solve ran the sweeps
+        }
     }
     return 0;
+#undef MERGE_EARLIER_CHUNKS
+#undef MERGE_WORD
 }
 
 // The launch forms.  (1) one workgroup per env of the batch (blockIdx = env), filtered by the active mask and -- under sticky tiers -- by

@@ -32,7 +32,7 @@ BatchKnobs read_knobs() {
 #ifndef UHC_EXPERIMENTS
     k.dbg &= ~0x1f00;  // bits 8-12 (working-set fill, consumer cap, sticky tier 4) are measurement switches of tools/ builds: the shipped library does not read them
 #endif
-    if (const char* m = getenv("UHC_TIER_MARKS")) sscanf(m, "%d,%d,%d,%d,%d,%d,%d,%d", k.marks, k.marks + 1, k.marks + 2, k.marks + 3, k.marks + 4, k.marks + 5, k.marks + 6, k.marks + 7);
+    if (const char* m = getenv("UHC_TIER_MARKS")) sscanf(m, "%d,%d,%d,%d,%d,%d,%d,%d", k.marks + UHC_MARK_UP2_ROWS, k.marks + UHC_MARK_UP2_CON, k.marks + UHC_MARK_UP2_TWO, k.marks + UHC_MARK_DN1_ROWS, k.marks + UHC_MARK_DN1_CON, k.marks + UHC_MARK_DN1_TWO, k.marks + UHC_MARK_UP3_8THS, k.marks + UHC_MARK_DN2_8THS);
     // UHC_FAST_DENSE = "KiB,dense rows[,contacts]": the dense fast tier's LDS budget, body-body row slots and contact capacity (experiments)
     if (const char* fd = getenv("UHC_FAST_DENSE")) k.fast_dense_got = sscanf(fd, "%d,%d,%d", &k.fast_dense_kib, &k.fast_dense_rows, &k.fast_dense_con);
     k.fast_dcol_own = is("UHC_FAST_DCOL_OWN", '1');
@@ -375,9 +375,9 @@ static void fast_layout(Carver& cv, const UhcModelDesc& d, int n_env, const Batc
     cv.end_guard();
     F.rowR = F.rowAref = F.rowB = F.rowF = F.rowDa = F.rowW = F.rowY = F.dsc = F.Y;  // unused by the fast kernel
     F.total = cv.off;
-    if (A.marks[2] < 0) {  // the marks follow the layout: up at the capacity, down with a little room to spare
-        A.marks[2] = A.cf.ndense > 0 ? A.cf.ndense : UHC_FAST_MAXTWO; A.marks[5] = A.cf.ndense > 0 ? std::max(1, A.cf.ndense - (A.cf.ndense > 8 ? 2 : 1)) : 10;
-        A.marks[1] = A.cf.maxcon; A.marks[4] = A.cf.maxcon - std::max(2, A.cf.maxcon / 8);
+    if (A.marks[UHC_MARK_UP2_TWO] < 0) {  // the marks follow the layout: up at the capacity, down with a little room to spare
+        A.marks[UHC_MARK_UP2_TWO] = A.cf.ndense > 0 ? A.cf.ndense : UHC_FAST_MAXTWO; A.marks[UHC_MARK_DN1_TWO] = A.cf.ndense > 0 ? std::max(1, A.cf.ndense - (A.cf.ndense > 8 ? 2 : 1)) : 10;
+        A.marks[UHC_MARK_UP2_CON] = A.cf.maxcon; A.marks[UHC_MARK_DN1_CON] = A.cf.maxcon - std::max(2, A.cf.maxcon / 8);
     }
     P.lds_bytes_fast = (size_t)cv.off * sizeof(double);
     if (knobs.lds_pad_fast) {  // UHC_LDS_PAD_FAST (read_knobs): the launch asks for more than the layout needs
@@ -634,7 +634,7 @@ int plan_batch(const UhcModel* const* models, int n_models, const int32_t* env_m
     // capacities) and comes down again at 56 / 14 / 10 and at 7/8 of the general tier's.  Going up EARLIER (at 3/4 of a capacity, so
     // that no env finds out in mid-step) was measured on the self-colliding rollout: 51-55 k env-steps/s against 57 k -- the envs
     // parked a tier up cost more than the late hand-ons they avoid (profiles/r03_marks_sweep.txt)
-    for (int k = 0; k < 8; k++) A.marks[k] = knobs.marks[k];  // (body-body rows, marks[2] < 0: set from the fast layout's dense slots unless UHC_TIER_MARKS names them)
+    for (int k = 0; k < UHC_N_MARKS; k++) A.marks[k] = knobs.marks[k];  // (body-body rows, marks[UHC_MARK_UP2_TWO] < 0: set from the fast layout's dense slots unless UHC_TIER_MARKS names them)
     Carver cv[4];  // the layout being carved: 0 fast, 1 general, 2 large, 3 tier 4
     for (Carver& c : cv) c.guard_on = knobs.guard != 0;
     fast_layout(cv[0], d, n_env, knobs, P);

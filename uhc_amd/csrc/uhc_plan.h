@@ -5,11 +5,12 @@
 #include <vector>
 
 #include "uhc_host.h"
+#include "uhc_step_words.h"
 
 // the UHC_* environment variables of batch creation, parsed and range-checked (read_knobs is the one place of the host code that reads the environment)
 struct BatchKnobs : QueueCaps {    // (the caps: UHC_Q2_DIV, UHC_Q2_WAIT, UHC_Q2_MAX, UHC_Q3_MAX, UHC_Q4_MAX)
     int dbg = 0;                    // UHC_DEBUG (KernelArgs::dbg; bits 8-12 only in -DUHC_EXPERIMENTS builds)
-    int marks[8] = {64, 16, -1, 56, 14, 10, 8, 7};  // UHC_TIER_MARKS "a,b,c,d,e,f,g,h" (marks[2] < 0: body-body marks follow the fast layout)
+    int marks[UHC_N_MARKS] = {64, 16, -1, 56, 14, 10, 8, 7};  // UHC_TIER_MARKS "a,b,c,d,e,f,g,h" in UhcMark's order (the body-body up mark < 0: the body-body marks follow the fast layout)
     int fast_dense_got = 0, fast_dense_kib = 0, fast_dense_rows = 0, fast_dense_con = 0;  // UHC_FAST_DENSE "KiB,dense rows[,contacts]": fields read, their values
     bool fast_dcol_own = false;     // UHC_FAST_DCOL_OWN=1
     bool lds_pad_fast = false;      // UHC_LDS_PAD_FAST=KiB

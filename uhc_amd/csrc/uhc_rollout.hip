@@ -73,13 +73,13 @@ __global__ void __launch_bounds__(1024) uhc_rollout_record_kernel(int n_env, int
         acc[0] += r;
         for (int k = 0; k < n_parts; k++) acc[1 + k] += parts[(size_t)e * parts_stride + k];
         if (redo) {  // UHC_F_REDO of the step: computed by the general kernel / its exact contact solve fell back to sweeps
-            acc[n_parts + 1] += (redo[e] & 1) != 0;
-            acc[n_parts + 2] += (redo[e] & 2) != 0;
-            acc[n_parts + 3] += (redo[e] & 0x80) != 0;  // rows / contacts beyond the last tier's capacity were dropped in THIS step
-            acc[n_parts + 4] += (redo[e] & 0x40) != 0;  // computed by the large tier
-            acc[n_parts + 5] += (redo[e] & 8) != 0;     // an island with more than 64 force-carrying rows: solved exactly in windows of 64
-            acc[n_parts + 6] += (redo[e] & (1 << 30)) != 0;  // (part of) the step solved by Newton on the primal: tier 4
-            acc[n_parts + 7] += (redo[e] & (1 << 29)) != 0;  // ... and that iteration stopped at its cap
+            acc[n_parts + 1] += (redo[e] & UHC_REDO_GENERAL) != 0;
+            acc[n_parts + 2] += (redo[e] & UHC_REDO_SWEPT) != 0;
+            acc[n_parts + 3] += (redo[e] & UHC_REDO_DROPPED) != 0;  // rows / contacts beyond the last tier's capacity were dropped in THIS step
+            acc[n_parts + 4] += (redo[e] & UHC_REDO_LARGE) != 0;  // computed by the large tier
+            acc[n_parts + 5] += (redo[e] & UHC_REDO_WINDOWED) != 0; // an island with more than 64 force-carrying rows: solved exactly in windows of 64
+            acc[n_parts + 6] += (redo[e] & UHC_REDO_PRIMAL) != 0;  // (part of) the step solved by Newton on the primal: tier 4
+            acc[n_parts + 7] += (redo[e] & UHC_REDO_PRIMAL_CAP) != 0;  // ... and that iteration stopped at its cap
         }
     }
     for (int k = 0; k < nacc; k++) {

@@ -10,6 +10,9 @@ import numpy as np
 import torch
 
 from ._capi import UhcCtrlDesc, UhcEnvDesc, model_desc
+from ._capi import (REDO_DROPPED, REDO_GENERAL, REDO_LARGE, REDO_PRIMAL, REDO_PRIMAL_CAP, REDO_SWEPT, REDO_SWEPT_SUBSTEP0, REDO_SWEPT_SUBSTEPS,  # noqa: F401 (re-exported next to F_*)
+                    REDO_WHY_FRICTION, REDO_WHY_NOCONV, REDO_WHY_PIVOT, REDO_WINDOWED, WHY_CANDIDATES, WHY_CONTACTS, WHY_DENSE_SLOTS, WHY_FAST_SHIFT, WHY_FIELD,
+                    WHY_GENERAL_SHIFT, WHY_LARGE_SHIFT, WHY_ROW_STORAGE, WHY_ROWS, WHY_SOLVER, WHY_SUBSTEP_SHIFT)
 from ._lib import check, lib
 
 F_QPOS, F_QVEL, F_XPOS, F_XQUAT, F_XIPOS, F_QM, F_QFRC_BIAS, F_QACC, F_CTRL = range(9)
