@@ -141,7 +141,11 @@ enum UhcField {
                               * working sets / a working set the pivoting could not solve); bit 8 + k: substep k (< 21) of the step was one of those
                               * (a checker that follows the same path needs to know which); bit 7: constraint rows / contacts beyond the LAST tier's
                               * capacity were DROPPED in this step (UHC_F_EFC_OVERFLOW is the sticky version, cleared by the env's next set_state);
-                              * without tier 4 a forward pass that dropped rows gets a bounded exact attempt and at most 32 sweeps (bits 1 and 7) */
+                              * without tier 4 a forward pass that dropped rows gets a bounded exact attempt and at most 32 sweeps (bits 1 and 7).
+                              * An env with friction-loss rows (dof_frictionloss > 0: box constraints) is solved by sweeps from the warm start at either solver, in
+                              * every tier: the fast tier does so without a word (the word stays 0); at solver 1 the general tier, the large tier and tier 4 report
+                              * bits 1 and 2 and the swept bit of every substep they computed, tier 4 without bit 30; at solver 0 the general and the large tier report
+                              * bit 1 and the substep bits without a reason -- as for any env at solver 0 -- and tier 4 reports neither */
     UHC_F_TIER = 17,         /* int32 [n_env] 1 | 2 | 3 | 4: the tier the env's next step starts in under uhc_batch_set_kernel_path(2) */
     UHC_F_HANDON_WHY = 18,   /* int32 [n_env] diagnostic of the last step: bits 0-7 why the fast tier handed the env on, bits 8-15 why the general tier did
                               * (1 contacts, 2 constraint rows, 4 body-body row slots, 8 packed row storage, 16 MPR candidate list beyond the tier's

@@ -1503,6 +1503,14 @@ int orc_get(const UhcModelDesc* m, const OrcData* d, const char* name, double* o
         for (int c = 0; c < d->ncon && c < max; c++) out[c] = g[c];
         return d->ncon;
     }
+    if (!strcmp(name, "efc_type")) { /* the rows' kinds (ORC_EFC_FRICTION = 1, LIMIT = 2, CONTACT = 3, CONTACT_PYR = 4), as doubles */
+        for (int r = 0; r < d->nefc && r < max; r++) out[r] = d->efc_type[r];
+        return d->nefc;
+    }
+    if (!strcmp(name, "efc_floss")) {
+        for (int r = 0; r < d->nefc && r < max; r++) out[r] = d->efc_floss[r];
+        return d->nefc;
+    }
     return -1;
 }
 int orc_get_int(const OrcData* d, const char* name) {

@@ -151,3 +151,108 @@ def caterpillar_model(n_seg=27, half=0.1, gap=0.02):
 </mujoco>
 """
     return compile_mjcf(xml, meshes={"seg": tris})
+
+
+def slider_model(axis=(1.0, 0.3, 0.2), limit=(-0.3, 0.4)):
+    """Slide joints on every side of a hinge, no contacts (contype 0): a 1 kg cart on a LIMITED slide whose axis is no coordinate axis (an unrotated or transposed axis
+    shows) and whose body carries a non-identity quat; the cart carries a pendulum arm on a hinge, and the arm a bob on a second slide -- a slide below a rotating parent, and
+    slide, hinge and slide dofs in one dof chain (the L^-T back substitution crosses both motion subspaces).  One motor per joint."""
+    from uhc_amd.model.mjcf import compile_mjcf
+    tris = box_triangles(0.03, 0.03, 0.03)
+    xml = f"""
+<mujoco>
+  <compiler angle="radian" coordinate="local"/>
+  <option timestep="0.002"/>
+  <default><geom contype="0" conaffinity="0" margin="0.001"/></default>
+  <asset><mesh name="cube" file="unused.stl"/></asset>
+  <worldbody>
+    <body name="cart" pos="0.1 -0.2 1.5" quat="0.9 0.1 0.3 0.2">
+      <inertial pos="0.01 0.02 -0.01" mass="1" diaginertia="0.02 0.015 0.01"/>
+      <joint name="rail" type="slide" axis="{axis[0]} {axis[1]} {axis[2]}" pos="0 0 0" limited="true" range="{limit[0]} {limit[1]}"/>
+      <geom type="mesh" mesh="cube"/>
+      <body name="arm" pos="0.02 0.05 -0.1" quat="0.98 0.05 -0.1 0.15">
+        <inertial pos="0.01 0 -0.25" mass="0.5" diaginertia="0.012 0.011 0.002"/>
+        <joint name="pivot" type="hinge" axis="0.1 1 0.2" pos="0 0 0.03"/>
+        <geom type="mesh" mesh="cube"/>
+        <body name="bob" pos="0 0.01 -0.3" quat="0.95 -0.2 0.1 0.1">
+          <inertial pos="0 0.01 0.02" mass="0.3" diaginertia="0.003 0.002 0.002"/>
+          <joint name="telescope" type="slide" axis="0.2 -0.1 1" pos="0.01 0 0"/>
+          <geom type="mesh" mesh="cube"/>
+        </body>
+      </body>
+    </body>
+  </worldbody>
+  <actuator><motor name="m_rail" joint="rail" gear="1"/><motor name="m_pivot" joint="pivot" gear="1"/><motor name="m_telescope" joint="telescope" gear="1"/></actuator>
+</mujoco>
+"""
+    return compile_mjcf(xml, meshes={"cube": tris})
+
+
+def cart_model(axis=(0.0, 0.0, 1.0), limit=None):
+    """One 1 kg body on ONE slide joint along `axis`, timestep 0.002, no contacts: the scene of the closed forms (weight against friction loss, a spring's period, a limit)."""
+    from uhc_amd.model.mjcf import compile_mjcf
+    lim = "" if limit is None else f'limited="true" range="{limit[0]} {limit[1]}"'
+    xml = f"""
+<mujoco>
+  <compiler angle="radian" coordinate="local"/>
+  <option timestep="0.002"/>
+  <default><geom contype="0" conaffinity="0" margin="0.001"/></default>
+  <asset><mesh name="cube" file="unused.stl"/></asset>
+  <worldbody>
+    <body name="cart" pos="0.3 0.2 1">
+      <inertial pos="0 0 0" mass="1" diaginertia="0.01 0.01 0.01"/>
+      <joint name="rail" type="slide" axis="{axis[0]} {axis[1]} {axis[2]}" pos="0 0 0" {lim}/>
+      <geom type="mesh" mesh="cube"/>
+    </body>
+  </worldbody>
+  <actuator><motor name="m_rail" joint="rail" gear="1"/></actuator>
+</mujoco>
+"""
+    return compile_mjcf(xml, meshes={"cube": box_triangles(0.03, 0.03, 0.03)})
+
+
+def with_passives(model, frictionloss=None, stiffness=None, qpos_spring=None):
+    """`model` with other passive joint terms (a dataclasses.replace: nothing derived depends on them).  Each of `frictionloss`, `stiffness` and `qpos_spring` is a scalar
+    -- given to every hinge and slide joint, the joints whose springs and friction loss the models of the configs set -- or an array with one value per joint, or one per dof
+    (`qpos_spring`: per entry of qpos).  None leaves the model's own values."""
+    import dataclasses
+    jt, ja, da = np.asarray(model.jnt_type), np.asarray(model.jnt_qposadr), np.asarray(model.jnt_dofadr)
+    scalar_jnt = (jt == 2) | (jt == 3)  # slide, hinge
+    dofs_of = [np.flatnonzero(np.asarray(model.dof_jntid) == j) for j in range(model.njnt)]
+    new = {}
+    if frictionloss is not None:
+        f = np.asarray(frictionloss, dtype=np.float64)
+        out = np.asarray(model.dof_frictionloss, dtype=np.float64).copy()
+        if f.ndim == 0:
+            for j in np.flatnonzero(scalar_jnt):
+                out[dofs_of[j]] = f
+        elif f.shape == (model.nv,):
+            out = f.copy()
+        else:
+            assert f.shape == (model.njnt,), f.shape
+            for j in range(model.njnt):
+                out[dofs_of[j]] = f[j]
+        new["dof_frictionloss"] = out
+    if stiffness is not None:
+        k = np.asarray(stiffness, dtype=np.float64)
+        out = np.asarray(model.jnt_stiffness, dtype=np.float64).copy()
+        if k.ndim == 0:
+            out[scalar_jnt] = k
+        elif k.shape == (model.njnt,):
+            out = k.copy()
+        else:  # per dof: a joint takes the value of its first dof
+            assert k.shape == (model.nv,), k.shape
+            out = k[da].copy()
+        new["jnt_stiffness"] = out
+    if qpos_spring is not None:
+        r = np.asarray(qpos_spring, dtype=np.float64)
+        out = np.asarray(model.qpos_spring, dtype=np.float64).copy()
+        if r.ndim == 0:
+            out[ja[scalar_jnt]] = r
+        elif r.shape == (model.nq,) and model.nq != model.njnt:
+            out = r.copy()
+        else:
+            assert r.shape == (model.njnt,), r.shape
+            out[ja[scalar_jnt]] = r[scalar_jnt]
+        new["qpos_spring"] = out
+    return dataclasses.replace(model, **new)

@@ -2602,7 +2602,8 @@ __device__ __forceinline__ FwdOut k_forward(const KernelArgs& A, const double* m
                 return out;
             }
             if (it < 0) {
-                if (T.solver == 1) {  // the working sets gave up: sweep from the warm start, as the reference's PGS does
+                if (T.solver == 1 && it != UHC_WS_FRICTION) {  // the working sets gave up: sweep from the warm start, as the reference's PGS does
+                    // (friction-loss rows: k_as_general returned before it touched the forces or saved them -- rowF still IS the warm start, rowW is whatever an earlier pass left)
                     for (int r = LANE; r < out.nefc; r += UHC_WAVE) S[L.rowF + r] = S[L.rowW + r];
                     wsync();
                 }

@@ -8,7 +8,7 @@ assets/mujoco_models/template/humanoid_template.xml, test.xml):
 
   compiler(angle, coordinate, inertiafromgeom) / default(joint, geom, motor)
   option(timestep, gravity, iterations, tolerance) / asset(mesh file=)
-  worldbody -> nested body(name,pos,quat) { joint(free|ball|hinge), geom(plane|mesh|box|sphere|capsule [size + pos/quat, or fromto]) }
+  worldbody -> nested body(name,pos,quat) { joint(free|ball|slide|hinge; stiffness, springref, frictionloss, damping, armature), geom(plane|mesh|box|sphere|capsule [size + pos/quat, or fromto]) }
   contact/exclude(body1, body2) / actuator/motor(joint, gear)
 
 MuJoCo 2.1.0 itself is not available to this build; every
@@ -606,6 +606,9 @@ def compile_mjcf(xml: str, asset_dir: str = ".", meshes: Optional[Dict[str, np.n
         j["damping"] = float(dfl.get("joint", e, "damping", 0.0))
         j["stiffness"] = float(dfl.get("joint", e, "stiffness", 0.0))
         j["frictionloss"] = float(dfl.get("joint", e, "frictionloss", 0.0))
+        j["springref"] = float(dfl.get("joint", e, "springref", 0.0))  # (MuJoCo's default is the joint's ref, which stays 0 here)
+        if degree and j["type"] == JNT_HINGE:
+            j["springref"] = float(np.deg2rad(j["springref"]))
         j["margin"] = float(dfl.get("joint", e, "margin", 0.0))
         if j["type"] == JNT_FREE:
             j["limited"] = False
@@ -758,6 +761,9 @@ def compile_mjcf(xml: str, asset_dir: str = ".", meshes: Optional[Dict[str, np.n
         if b["joints"]:
             last_dof_of_body[bid] = da - 1
     m.qpos_spring = m.qpos0.copy()
+    for jid, j in enumerate(joints):  # springref: the spring's rest position of a hinge / slide (ball and free joints rest at qpos0)
+        if j["type"] in (JNT_SLIDE, JNT_HINGE):
+            m.qpos_spring[m.jnt_qposadr[jid]] = j["springref"]
     # sparse-M row addresses: row i holds (i, parent(i), parent(parent(i)), ...) [MJ-ext qM layout]
     m.dof_madr = np.zeros(m.nv + 1, dtype=np.int32)
     for i in range(m.nv):
@@ -1250,7 +1256,7 @@ def export_mjcf(m: Model, density: Optional[float] = None) -> str:
             out.append(f'{ind}  <joint name="{name}" type="{kind}" pos="{f(m.jnt_pos[j])}" axis="{f(m.jnt_axis[j])}" '
                        f'limited="{"true" if m.jnt_limited[j] else "false"}" range="{f(m.jnt_range[j])}" armature="{float(m.dof_armature[d])!r}" '
                        f'damping="{float(m.dof_damping[d])!r}" frictionloss="{float(m.dof_frictionloss[d])!r}" stiffness="{float(m.jnt_stiffness[j])!r}" '
-                       f'margin="{float(m.jnt_margin[j])!r}"/>')
+                       f'margin="{float(m.jnt_margin[j])!r}"' + (f' springref="{float(m.qpos_spring[int(m.jnt_qposadr[j])])!r}"/>' if t != JNT_BALL else "/>"))
         geoms_of(b, ind + "  ")
         for c in children[b]:
             emit(c, ind + "  ")
