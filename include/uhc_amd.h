@@ -126,7 +126,7 @@ enum UhcField {
     UHC_F_SOLVER_ITER = 12, /* int32 [n_env] PGS sweeps used by the last solve */
     UHC_F_QFRC_APPLIED = 13, /* [n_env][nv] data.qfrc_applied of the last substep */
     UHC_F_EFC_OVERFLOW = 14, /* int32 [n_env] sticky: constraint rows were dropped (nefc cap) */
-    UHC_F_STAGE_PROF = 15,   /* int64 [n_env][40] per-stage shader-cycle counters (profiling builds only) */
+    UHC_F_STAGE_PROF = 15,   /* int64 [n_env][UHC_PROF_WORDS] per-stage shader-cycle counters (profiling builds), or the tier trace (UhcTraceWord) */
     UHC_F_REDO = 16,         /* int32 [n_env] bit 0: the env's last step / forward pass exceeded the fast tier's capacity (64 rows, 16 contacts, packed
                               * row storage, 12 body-body rows) and was computed by the general tier (128 rows, 64 contacts, 20 body-body rows), the
                               * large one (256 / 128 / 32; bit 6) or tier 4 (up to 1024 rows / 192-320 contacts / 128 body-body rows, by what the LDS holds beside the Hessian; bits 6 and 30), all of
@@ -181,9 +181,47 @@ enum UhcField {
 #define UHC_HANDON_CANDIDATES 16
 #define UHC_HANDON_SOLVER 32
 
+/* UHC_DEBUG in the environment of uhc_batch_create: debug switches, OR-ed (KernelArgs::dbg) */
+enum UhcDebug {
+    UHC_DEBUG_NO_MERGE = 1 << 0,        /* the working sets never merge islands */
+    UHC_DEBUG_NO_VSTAGE = 1 << 1,       /* MPR's vertices are not staged in LDS */
+    UHC_DEBUG_RESTART_HANDON = 1 << 2,  /* a handed-on env restarts its step instead of resuming at the substep (only the whole-step launch can: no chunks) */
+    UHC_DEBUG_ENV_ORDER = 1 << 3,       /* the sticky fast tier launches in env order */
+    UHC_DEBUG_TRACE = 1 << 4,           /* tier trace in the stage-profile record (UhcTraceWord; tools/tier_trace.py) */
+    UHC_DEBUG_NO_GATE = 1 << 5,         /* no gate before the fast tier's launch */
+    UHC_DEBUG_LOG = 1 << 6,             /* log the queue lengths and the gate's wait per step, and tier 4's layout, to stderr */
+    UHC_DEBUG_NO_BOX_CULL = 1 << 7,     /* no box cull of the convex pairs */
+    /* Measurement switches: they change which envs report windows / sweeps in UHC_F_REDO, and exist only in libraries built with -DUHC_EXPERIMENTS (tools/ A/B
+     * builds).  The shipped library compiles their reads out (UHC_EXP, uhc_physics_impl.h) and masks the bits (uhc_plan.cpp); uhc_build_flags() bit 0 tells which kind a library is. */
+    UHC_DEBUG_EXP_NO_RANK_FILL = 1 << 8,   /* the general tier's first working set is NOT filled by rank (k_as_general; A/B of DESIGN 2) */
+    UHC_DEBUG_EXP_FILL_48 = 1 << 9,        /* ... fill 48 lanes instead of 64 */
+    UHC_DEBUG_EXP_FILL_56 = 1 << 10,       /* ... fill 56 */
+    UHC_DEBUG_EXP_FIXED_CAP2 = 1 << 11,    /* a fixed cap UHC_Q2_MAX on the general tier's consumers (plan_sticky_step, uhc_plan.cpp) */
+    UHC_DEBUG_EXP_STICKY_TIER4 = 1 << 12   /* sticky tier 4: an env whose step ended in tier 4 starts its next step there, at the head of the tier-4 consumers' queue
+                                            * (next_tier, uhc_step_words.h; measured and not the default) */
+};
+#define UHC_DEBUG_EXP_MASK (UHC_DEBUG_EXP_NO_RANK_FILL | UHC_DEBUG_EXP_FILL_48 | UHC_DEBUG_EXP_FILL_56 | UHC_DEBUG_EXP_FIXED_CAP2 | UHC_DEBUG_EXP_STICKY_TIER4)
+
+/* UHC_F_STAGE_PROF: UHC_PROF_WORDS int64 words per env, in two uses that overlay each other.  A library built with -DUHC_STAGE_PROF accumulates shader cycles per
+ * stage in words 0 .. 39 (the stages' names: tools/stage_profile.py NAMES).  The shipped library writes the TIER TRACE there under UHC_DEBUG_TRACE: 100 MHz wall-clock
+ * stamps and substeps of one control step, in the words below (the reader clears the record per step). */
+#define UHC_PROF_WORDS 40
+enum UhcTraceWord {
+    UHC_TRACE_TAKEN = 0,           /* + 2 (tier - 1), tiers 1-3: when the tier took the env up */
+    UHC_TRACE_LET_GO = 1,          /* + 2 (tier - 1), tiers 1-3: when it let the env go (done, or handed on) */
+    UHC_TRACE_HANDON_SUBSTEP = 6,  /* + (tier - 1), tiers 1, 2: the substep at which the tier handed the env on */
+    UHC_TRACE_CONSUMER = 8,        /* + UHC_TRACE_CONSUMER_WORDS (tier - 2), tiers 2, 3, in the record of env blockIdx: a queue consumer's own entry, first env claimed, exit, envs processed */
+    UHC_TRACE_GATE = 16,           /* in the record of the LAST env, 5 words: the gate's start, its end, consumers reported in at its start / end, of how many */
+    UHC_TRACE_TAKEN4 = 21,         /* tier 4's own stamps */
+    UHC_TRACE_LET_GO4 = 22,
+    UHC_TRACE_HANDON_SUBSTEP3 = 23,  /* the substep at which the large tier handed the env on to tier 4 */
+    UHC_TRACE_CHUNK_WAIT = 24      /* the fast tier in chunks: ticks the env's later chunks spent waiting for the previous one (summed) */
+};
+#define UHC_TRACE_CONSUMER_WORDS 4
+
 const char* uhc_last_error(void);
 int32_t uhc_abi_version(void);
-/* Which kind of build the library is: bit 0 = the solver's measurement switches (UHC_DEBUG bits 8-12) are compiled in (-DUHC_EXPERIMENTS, tools/ builds only),
+/* Which kind of build the library is: bit 0 = the solver's measurement switches (UHC_DEBUG_EXP_*) are compiled in (-DUHC_EXPERIMENTS, tools/ builds only),
  * bit 1 = per-stage cycle counters (-DUHC_STAGE_PROF), bit 2 = poisoned LDS, bit 3 = LDS guard words.  0 for the shipped library: a stray UHC_DEBUG cannot
  * change which solver path an env takes (tests/test_capi_symbols.py). */
 int32_t uhc_build_flags(void);

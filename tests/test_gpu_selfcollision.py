@@ -211,8 +211,8 @@ def test_sticky_tiers_follow_the_scene(model, standing):
 def test_hand_on_resumes_at_the_substep(model, standing):
     """A tier that finds an env too big in the middle of a control step hands it on WITH the substeps it has done: the next tier goes on
     from the substep that did not fit.  Self-colliding humanoids dropped from 2-7 cm: the feet land during the third or fourth control step, and the
-    impact takes the rows past 64 in one of its substeps.  The tier trace (UHC_DEBUG bit 4) shows hand-ons at a substep >= 1; the states equal those of a build
-    switch that makes the next tier repeat the step (bit 2) up to the rounding of the tiers' solvers, and follow the oracle."""
+    impact takes the rows past 64 in one of its substeps.  The tier trace (DEBUG_TRACE) shows hand-ons at a substep >= 1; the states equal those of a build
+    switch that makes the next tier repeat the step (DEBUG_RESTART_HANDON) up to the rounding of the tiers' solvers, and follow the oracle."""
     import torch
     from oracle.physics import OracleSim
     from uhc_amd import sim as S
@@ -230,9 +230,9 @@ def test_hand_on_resumes_at_the_substep(model, standing):
     qvel = np.zeros((n, 75))
     old = os.environ.get("UHC_DEBUG")
     try:
-        os.environ["UHC_DEBUG"] = "16"
+        os.environ["UHC_DEBUG"] = str(S.DEBUG_TRACE)
         resume = S.SimBatch(sc, ctrl, n)
-        os.environ["UHC_DEBUG"] = "20"
+        os.environ["UHC_DEBUG"] = str(S.DEBUG_TRACE | S.DEBUG_RESTART_HANDON)
         restart = S.SimBatch(sc, ctrl, n)
     finally:
         if old is None:
@@ -255,7 +255,7 @@ def test_hand_on_resumes_at_the_substep(model, standing):
             bb.sync()
         redo, gq = resume.field(S.F_REDO).cpu().numpy(), resume.field(S.F_QPOS).cpu().numpy()
         tr = resume.field(S.F_STAGE_PROF).cpu().numpy()
-        substeps.append(np.where((redo & REDO_GENERAL) != 0, tr[:, 6], -1))  # word 6 of the trace: the substep the fast tier handed the env on in
+        substeps.append(np.where((redo & REDO_GENERAL) != 0, tr[:, S.TRACE_HANDON_SUBSTEP], -1))  # the substep the fast tier handed the env on in
         apart = max(apart, np.abs(gq - restart.field(S.F_QPOS).cpu().numpy()).max())
         for e in range(n):
             os_[e].do_simulation(act[e], qpos[e, 7:], redo=redo[e])
@@ -576,7 +576,7 @@ def test_tier_4_consumers_take_what_the_large_tiers_consumers_hand_on(model, sta
     """Kernel path 2 with ALL the queues running: ten envs standing with the boxes far above them (kept in the general tier by UHC_TIER_MARKS, so that its
     queue has envs of its own and the consumers of every tier are launched), two face down beside the raft on the floor (large tier by stickiness; its
     consumer finds them too big in the first substep and appends them to tier 4's queue, whose consumers -- uhc_k_huge_q.hip -- take them up while the
-    other launches still run).  Every env re-posed each step; against the oracle, step by step; the library's own log (UHC_DEBUG bit 6) says whether
+    other launches still run).  Every env re-posed each step; against the oracle, step by step; the library's own log (DEBUG_LOG) says whether
     the tier-4 consumers were launched."""
     import dataclasses
     import torch
@@ -587,7 +587,7 @@ def test_tier_4_consumers_take_what_the_large_tiers_consumers_hand_on(model, sta
     from uhc_amd.sim import make_ctrl
     if os.environ.get("UHC_FORCE_GENERAL") == "1" or os.environ.get("UHC_TIERS") in ("2", "3"):
         pytest.skip("needs the fast tier to start from and tier 4 to end in")
-    monkeypatch.setenv("UHC_DEBUG", "64")
+    monkeypatch.setenv("UHC_DEBUG", str(S.DEBUG_LOG))
     monkeypatch.setenv("UHC_TIER_MARKS", "8,2,1,4,1,0,8,7")  # up to the general tier beyond 8 rows / 2 contacts / 1 body-body row; down again only below 4 / 1 / 0
     K = 7
     m = self_collision_variant(model)
@@ -690,7 +690,7 @@ def test_a_dof_chain_of_32_entries_goes_through_tier_4(monkeypatch, capfd):
     assert worst < 1e-8, worst
     b.close()
     # ---- sticky queues with every tier's consumers: the flat animals through tier 4's four-wave consumers
-    monkeypatch.setenv("UHC_DEBUG", "64")
+    monkeypatch.setenv("UHC_DEBUG", str(S.DEBUG_LOG))
     n, flat = 6, (1, 4)
     q = np.stack([pose(e not in flat) for e in range(n)])
     v = np.zeros((n, m.nv))

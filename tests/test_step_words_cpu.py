@@ -7,7 +7,7 @@ a. Equality with tests/step_words_recording.json: what the expressions of the co
    their own last_tier -- 2 and 3 among them (UHC_TIERS).
 b. Invariants nothing else states: where each status bit lands in UHC_F_REDO, the hysteresis of the tiers, monotonicity of the policy, the fresh env's place,
    the chunk record's merge.
-c. include/uhc_amd.h's UHC_REDO_* / UHC_HANDON_* against uhc_amd/sim.py's REDO_* / WHY_*."""
+c. include/uhc_amd.h's UHC_REDO_* / UHC_HANDON_* against uhc_amd/sim.py's REDO_* / WHY_*; its UHC_DEBUG_* / UHC_TRACE_* against DEBUG_* / TRACE_*."""
 import ctypes as C
 import itertools
 import json
@@ -406,4 +406,32 @@ def test_python_names_equal_the_header(words):
         defs[name] = 1 << int(m.group(1)) if m else int(val, 0)
     mine = {("UHC_" + k if k.startswith("REDO_") else "UHC_HANDON_" + k[4:]): v for k, v in vars(S).items() if k.startswith(("REDO_", "WHY_")) and isinstance(v, int)}
     assert len(defs) == 23 and mine == defs
+    assert "UHC_ABI_VERSION 11" in src  # naming the bits changed none of them
+
+
+def test_python_debug_bits_and_trace_words_equal_the_header():
+    """enum UhcDebug, enum UhcTraceWord, UHC_DEBUG_EXP_MASK, UHC_PROF_WORDS and UHC_TRACE_CONSUMER_WORDS of include/uhc_amd.h against uhc_amd/_capi.py's DEBUG_* / TRACE_* /
+    PROF_WORDS, and uhc_amd/sim.py's re-exports"""
+    from uhc_amd import _capi
+    S = _public()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "uhc_amd.h")).read(), flags=re.S)
+    defs = {}
+    for enum in ("UhcDebug", "UhcTraceWord"):
+        body = re.search(r"enum %s \{(.*?)\};" % enum, src, flags=re.S).group(1)
+        entries = [e.strip() for e in body.split(",") if e.strip()]
+        for e in entries:
+            name, val = re.fullmatch(r"(UHC_[A-Z0-9_]+) = (1 << \d+|\d+)", e).groups()
+            defs[name] = 1 << int(val[5:]) if val.startswith("1 << ") else int(val)
+    for name in ("UHC_PROF_WORDS", "UHC_TRACE_CONSUMER_WORDS"):
+        defs[name] = int(re.search(r"#define %s (\d+)\s" % name, src).group(1))
+    mask = re.search(r"#define UHC_DEBUG_EXP_MASK \((.*?)\)\n", src).group(1).split(" | ")
+    defs["UHC_DEBUG_EXP_MASK"] = sum(defs[n] for n in mask)
+    assert len(mask) == len(set(mask)) == 5 and defs["UHC_DEBUG_EXP_MASK"] == 0x1f00
+    assert [defs[n] for n in defs if n.startswith("UHC_DEBUG_") and n != "UHC_DEBUG_EXP_MASK"] == [1 << k for k in range(13)]  # thirteen bits, in order
+    for mod in (_capi, S):
+        mine = {"UHC_" + k: v for k, v in vars(mod).items() if k.startswith(("DEBUG_", "TRACE_", "PROF_WORDS")) and isinstance(v, int)}
+        assert len(defs) == 13 + 9 + 3 and mine == defs, (mod.__name__, set(mine.items()) ^ set(defs.items()))
+    # today's numbers: the record's length, the trace's words
+    assert (defs["UHC_PROF_WORDS"], defs["UHC_TRACE_TAKEN"], defs["UHC_TRACE_LET_GO"], defs["UHC_TRACE_HANDON_SUBSTEP"], defs["UHC_TRACE_CONSUMER"], defs["UHC_TRACE_GATE"], defs["UHC_TRACE_TAKEN4"],
+            defs["UHC_TRACE_LET_GO4"], defs["UHC_TRACE_HANDON_SUBSTEP3"], defs["UHC_TRACE_CHUNK_WAIT"]) == (40, 0, 1, 6, 8, 16, 21, 22, 23, 24)
     assert "UHC_ABI_VERSION 11" in src  # naming the bits changed none of them

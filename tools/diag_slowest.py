@@ -39,12 +39,12 @@ def main():
     torch.cuda.synchronize()
     prof = env.sim.field(S.F_STAGE_PROF)
     n = env.n_env
-    acc_all, acc_slow, n_all, tot_slow, tot_all, tot_fast, nefc_slow = np.zeros(40), np.zeros(40), 0, [], [], [], []
+    acc_all, acc_slow, n_all, tot_slow, tot_all, tot_fast, nefc_slow = np.zeros(S.PROF_WORDS), np.zeros(S.PROF_WORDS), 0, [], [], [], []
     for _ in range(steps):
         prof.zero_()
         agent.rollout_step()
         torch.cuda.synchronize()
-        p = prof.cpu().numpy().reshape(n, 40).astype(np.float64)
+        p = prof.cpu().numpy().reshape(n, S.PROF_WORDS).astype(np.float64)
         redo = env.sim.field(S.F_REDO).cpu().numpy()
         nefc = env.sim.field(S.F_NEFC).cpu().numpy()
         top = p[:, :16].sum(1)

@@ -1,6 +1,6 @@
 """Where one control step's time goes ACROSS the tiers (sticky tiers, self-colliding rollout): per env, when each tier took it up and
-let it go, and at which substep it was handed on.  Needs UHC_DEBUG bit 4 (set here): the product kernel then stamps a 100 MHz wall
-clock into the first words of the env's stage-profile record (uhc_physics_impl.h, TRACE).
+let it go, and at which substep it was handed on.  Needs UHC_DEBUG's DEBUG_TRACE (set here): the product kernel then stamps a 100 MHz wall
+clock into the first words of the env's stage-profile record (uhc_physics_impl.h, TRACE; the words: enum UhcTraceWord, include/uhc_amd.h).
 
   python tools/tier_trace.py [out.txt] [flags of bench.py]           the self-colliding rollout (bench line `self_collision`)
   TRACE_BALL=1 python tools/tier_trace.py [out.txt]                   the ball-joint humanoid's rollout (`ball_rollout`)
@@ -9,8 +9,10 @@ clock into the first words of the env's stage-profile record (uhc_physics_impl.h
 import os
 import sys
 
-os.environ["UHC_DEBUG"] = str(int(os.environ.get("UHC_DEBUG", "0")) | 16)
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from uhc_amd._capi import DEBUG_TRACE  # (plain constants: nothing is loaded yet)
+
+os.environ["UHC_DEBUG"] = str(int(os.environ.get("UHC_DEBUG", "0")) | DEBUG_TRACE)
 import numpy as np
 import torch
 
@@ -19,8 +21,8 @@ from uhc_amd import sim as S
 
 
 def analyze(prof, n, step, lines):
-    t = prof[:, :8].cpu().numpy().astype(np.float64)
-    stamps = t[:, :6]
+    t = prof[:, :S.TRACE_CONSUMER].cpu().numpy().astype(np.float64)  # tiers 1-3: taken up / let go, then the hand-on substeps of tiers 1, 2
+    stamps = t[:, :S.TRACE_HANDON_SUBSTEP]
     t0 = stamps[stamps > 0].min()
     ms = np.where(stamps > 0, (stamps - t0) * 1e-5, np.nan)  # 100 MHz -> ms
     end = np.nanmax(ms, axis=1)
@@ -34,9 +36,9 @@ def analyze(prof, n, step, lines):
             continue
         q = lambda x: " ".join(f"{v:6.2f}" for v in np.nanpercentile(x, [0, 25, 50, 75, 90, 99, 100]))
         lines.append(f"tier {tier}: {m.sum():4d} envs | start  (min 25% 50% 75% 90% 99% max) {q(s[m])} | end {q(e[m])} | duration {q((e - s)[m])}")
-    # the fast tier in substep chunks (UHC_FAST_CHUNK): tier 1's start is the first chunk's, its end the last chunk's (or the hand-on); word 24 sums the ticks the
+    # the fast tier in substep chunks (UHC_FAST_CHUNK): tier 1's start is the first chunk's, its end the last chunk's (or the hand-on); TRACE_CHUNK_WAIT sums the ticks the
     # env's later chunks spent waiting for the previous one (their workgroups hold a place meanwhile)
-    cw = prof[:, 24].cpu().numpy().astype(np.float64) * 1e-5
+    cw = prof[:, S.TRACE_CHUNK_WAIT].cpu().numpy().astype(np.float64) * 1e-5
     if (cw > 0).any():
         m1 = ~np.isnan(ms[:, 0])
         lines.append(f"tier 1 in chunks: {int((cw > 0).sum())} envs waited between chunks | place-ms spent waiting per env (min 25% 50% 75% 90% 99% max) "
@@ -44,14 +46,14 @@ def analyze(prof, n, step, lines):
     h1 = ~np.isnan(ms[:, 2]) & ~np.isnan(ms[:, 0])   # handed on by tier 1 this step
     if h1.any():
         wait = ms[h1, 2] - ms[h1, 1]
-        lines.append(f"handed on by tier 1: {h1.sum()} envs; at substep (mean) {t[h1, 6].mean():.1f}; hand-on time {np.percentile(ms[h1, 1], [0, 50, 100]).round(2).tolist()} ms;"
+        lines.append(f"handed on by tier 1: {h1.sum()} envs; at substep (mean) {t[h1, S.TRACE_HANDON_SUBSTEP].mean():.1f}; hand-on time {np.percentile(ms[h1, 1], [0, 50, 100]).round(2).tolist()} ms;"
                      f" wait for a consumer {np.percentile(wait, [0, 50, 100]).round(2).tolist()} ms")
     h2 = ~np.isnan(ms[:, 4]) & ~np.isnan(ms[:, 2])
     if h2.any():
         wait = ms[h2, 4] - ms[h2, 3]
-        lines.append(f"handed on by tier 2: {h2.sum()} envs; at substep (mean) {t[h2, 7].mean():.1f}; hand-on time {np.percentile(ms[h2, 3], [0, 50, 100]).round(2).tolist()} ms;"
+        lines.append(f"handed on by tier 2: {h2.sum()} envs; at substep (mean) {t[h2, S.TRACE_HANDON_SUBSTEP + 1].mean():.1f}; hand-on time {np.percentile(ms[h2, 3], [0, 50, 100]).round(2).tolist()} ms;"
                      f" wait for a consumer {np.percentile(wait, [0, 50, 100]).round(2).tolist()} ms")
-    t4 = prof[:, 21:24].cpu().numpy().astype(np.float64)  # tier 4's own stamps (taken up, let go) and the substep at which the large tier handed the env on
+    t4 = prof[:, S.TRACE_TAKEN4:S.TRACE_HANDON_SUBSTEP3 + 1].cpu().numpy().astype(np.float64)  # tier 4's own stamps (taken up, let go) and the substep at which the large tier handed the env on
     m4 = t4[:, 0] > 0
     if m4.any():
         s4, e4 = (t4[m4, 0] - t0) * 1e-5, (t4[m4, 1] - t0) * 1e-5
@@ -59,9 +61,10 @@ def analyze(prof, n, step, lines):
                      f" | handed on by the large tier at substep {t4[m4, 2].astype(int).tolist()}")
         end = np.where(m4, np.fmax(end, (t4[:, 1] - t0) * 1e-5), end)
         lines.append(f"        (with tier 4's envs the step ends at {np.nanmax(end):.2f} ms)")
-    full = prof[:, :16].cpu().numpy().astype(np.float64)
-    for tier, o in ((2, 8), (3, 12)):
-        c = full[:, o:o + 4]
+    full = prof[:, :S.TRACE_GATE].cpu().numpy().astype(np.float64)
+    for tier in (2, 3):
+        o = S.TRACE_CONSUMER + S.TRACE_CONSUMER_WORDS * (tier - 2)
+        c = full[:, o:o + S.TRACE_CONSUMER_WORDS]
         m = c[:, 0] > 0
         if m.any():
             rel = lambda x: (x - t0) * 1e-5
@@ -69,14 +72,14 @@ def analyze(prof, n, step, lines):
             lines.append(f"tier {tier} consumers: {m.sum()} workgroups; entry {np.percentile(rel(c[m, 0]), [0, 50, 100]).round(2).tolist()} ms; first env claimed "
                          f"{np.nanpercentile(first, [0, 50, 100]).round(2).tolist() if (~np.isnan(first)).any() else 'never'} ms ({int(np.isnan(first).sum())} never); "
                          f"exit {np.percentile(rel(c[m, 2]), [0, 50, 100]).round(2).tolist()} ms; envs per workgroup {np.percentile(c[m, 3], [0, 50, 100]).tolist()}")
-    g = prof[n - 1, 16:21].cpu().numpy().astype(np.float64)
+    g = prof[n - 1, S.TRACE_GATE:S.TRACE_GATE + 5].cpu().numpy().astype(np.float64)
     if g[0] > 0:
         lines.append(f"gate: from {(g[0] - t0) * 1e-5:.3f} to {(g[1] - t0) * 1e-5:.3f} ms; consumers reported in at its start / end {int(g[2])} / {int(g[3])} of {int(g[4])}")
     worst = np.argsort(-end)[:6]
     for w in worst:
         lines.append(f"  env {w:4d} ends {end[w]:6.2f} ms: " + " ".join(
             f"T{k + 1}[{ms[w, 2 * k]:.2f}..{ms[w, 2 * k + 1]:.2f}]" for k in range(3) if not np.isnan(ms[w, 2 * k])) +
-            f" hand-on substeps {int(t[w, 6])} {int(t[w, 7])}")
+            f" hand-on substeps {int(t[w, S.TRACE_HANDON_SUBSTEP])} {int(t[w, S.TRACE_HANDON_SUBSTEP + 1])}")
 
 
 def main():

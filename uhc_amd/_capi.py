@@ -12,6 +12,13 @@ REDO_SWEPT_SUBSTEP0, REDO_SWEPT_SUBSTEPS = 1 << 8, 21  # REDO_SWEPT_SUBSTEP0 << 
 REDO_PRIMAL_CAP, REDO_PRIMAL = 1 << 29, 1 << 30
 WHY_FIELD, WHY_FAST_SHIFT, WHY_GENERAL_SHIFT, WHY_SUBSTEP_SHIFT, WHY_LARGE_SHIFT = 0xff, 0, 8, 16, 24
 WHY_CONTACTS, WHY_ROWS, WHY_DENSE_SLOTS, WHY_ROW_STORAGE, WHY_CANDIDATES, WHY_SOLVER = (1 << k for k in range(6))
+# the bits of UHC_DEBUG (enum UhcDebug; DEBUG_EXP_*: measurement switches of -DUHC_EXPERIMENTS builds) and the tier trace's words in the F_STAGE_PROF record (enum UhcTraceWord)
+(DEBUG_NO_MERGE, DEBUG_NO_VSTAGE, DEBUG_RESTART_HANDON, DEBUG_ENV_ORDER, DEBUG_TRACE, DEBUG_NO_GATE, DEBUG_LOG, DEBUG_NO_BOX_CULL,
+ DEBUG_EXP_NO_RANK_FILL, DEBUG_EXP_FILL_48, DEBUG_EXP_FILL_56, DEBUG_EXP_FIXED_CAP2, DEBUG_EXP_STICKY_TIER4) = (1 << k for k in range(13))
+DEBUG_EXP_MASK = DEBUG_EXP_NO_RANK_FILL | DEBUG_EXP_FILL_48 | DEBUG_EXP_FILL_56 | DEBUG_EXP_FIXED_CAP2 | DEBUG_EXP_STICKY_TIER4
+PROF_WORDS = 40
+TRACE_TAKEN, TRACE_LET_GO, TRACE_HANDON_SUBSTEP, TRACE_CONSUMER, TRACE_GATE = 0, 1, 6, 8, 16  # (+ 2 (tier - 1), the same, + (tier - 1), + TRACE_CONSUMER_WORDS (tier - 2), -)
+TRACE_TAKEN4, TRACE_LET_GO4, TRACE_HANDON_SUBSTEP3, TRACE_CHUNK_WAIT, TRACE_CONSUMER_WORDS = 21, 22, 23, 24, 4
 
 _I32P = C.POINTER(C.c_int32)
 _F64P = C.POINTER(C.c_double)

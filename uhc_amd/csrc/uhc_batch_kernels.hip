@@ -51,7 +51,7 @@ extern "C" hipError_t uhc_launch_set_state(const DevState* s, int nq, int nv, in
 // sticky tiers, head of a control step: snapshot of the tier table + the queues of the general / large tier, which start with the active
 // envs that begin the step there (lists UHC_LIST_GEN, UHC_LIST_BIG of n_env slots each, free slots = -1; counts UHC_CNT_GEN, UHC_CNT_BIG),
 // the cursors the persistent launches share and the counters their workgroups bump (UhcFin).  The words' names: uhc_device.h
-// (tier 4, `launch4` != 0: tier 4's queue consumers run this step; the envs whose last step ended in tier 4 (UHC_DEBUG bit 12 only) head their queue -- list UHC_LIST_T4,
+// (tier 4, `launch4` != 0: tier 4's queue consumers run this step; the envs whose last step ended in tier 4 (UHC_DEBUG_EXP_STICKY_TIER4 only) head their queue -- list UHC_LIST_T4,
 //  count UHC_CNT_T4 -- and are flagged pend3 = 2, "straight to tier 4"; with launch4 == 0 they are the large tier's like any tier-3 env and the snapshot says 3)
 __global__ void uhc_tier_lists_kernel(const int* tier, const int* d_active, int n_env, int* tier_now, int* lists, int* counts, int* cursors, int* fin,
                                       const int* cost, const int* fresh, int* order, int launch4, int* pend3) {

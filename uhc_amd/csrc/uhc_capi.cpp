@@ -63,7 +63,7 @@ static int fail(const char* fmt, ...) {
 
 extern "C" const char* uhc_last_error(void) { return g_err.c_str(); }
 extern "C" int32_t uhc_abi_version(void) { return UHC_ABI_VERSION; }
-// what kind of build this library is: bit 0 = the solver's measurement switches are compiled in (-DUHC_EXPERIMENTS: UHC_DEBUG bits 8-12 act), bit 1 = stage
+// what kind of build this library is: bit 0 = the solver's measurement switches are compiled in (-DUHC_EXPERIMENTS: UHC_DEBUG_EXP_* act), bit 1 = stage
 // cycle counters (-DUHC_STAGE_PROF), bit 2 = poisoned LDS (-DUHC_POISON_LDS), bit 3 = LDS guard words (-DUHC_GUARD_LDS).  The shipped library returns 0.
 extern "C" int32_t uhc_build_flags(void) {
     int32_t f = 0;
@@ -229,7 +229,7 @@ static int alloc_state(UhcBatch* b, const UhcModel* const* models, const int32_t
     TRY(dalloc(b, W.total, &S.redo)); S.pend2 = S.redo + W.pend2; S.pend3 = S.redo + W.pend3; S.resume = S.redo + W.resume; S.why = S.redo + W.why;
     A.chunk_done = S.redo + W.chunk_done; A.ticket = S.redo + W.ticket; TRY(dalloc(b, E * UHC_CHUNK_REC, &A.chunk_rec));
     TRY(dalloc(b, E, &S.tier)); TRY(dalloc(b, E, &b->tier_now)); S.tier_now = b->tier_now; TRY(dalloc(b, E, &S.cost));
-    if (!(A.dbg & 8)) TRY(dalloc(b, E, &b->d_order));  // (UHC_DEBUG bit 3: the fast tier launches in env order)
+    if (!(A.dbg & UHC_DEBUG_ENV_ORDER)) TRY(dalloc(b, E, &b->d_order));
     TRY(dalloc(b, UHC_N_LISTS * E, &b->d_lists)); TRY(dalloc(b, UHC_N_WORDS, &b->d_counts)); TRY(dalloc(b, UHC_N_WORDS, &b->d_cursors)); TRY(dalloc(b, UHC_N_WORDS, &b->d_fin));
     { std::vector<int> one(E, 1); HIP_OK(hipMemcpy(S.tier, one.data(), E * sizeof(int), hipMemcpyHostToDevice)); } TRY(dalloc(b, E, &S.fresh)); TRY(dalloc(b, E * UHC_NPROF, &S.prof)); TRY(dalloc(b, E * nv, &S.bias)); TRY(dalloc(b, E * nu, &S.ctrl));
     TRY(dalloc(b, E * nv, &S.applied));
@@ -282,7 +282,7 @@ extern "C" int32_t uhc_batch_create(const UhcModel* const* models, int32_t n_mod
     b->use_fast = P.use_fast;
     b->hbm_guard = knobs.guard != 0;
     b->caps = knobs;
-    b->fast_chunk = (P.A.dbg & 4) ? 0x7fff : knobs.fast_chunk;  // (UHC_DEBUG bit 2 restarts a handed-on env's step from substep 0: only the whole-step launch can)
+    b->fast_chunk = (P.A.dbg & UHC_DEBUG_RESTART_HANDON) ? 0x7fff : knobs.fast_chunk;  // (a handed-on env's step restarts from substep 0: only the whole-step launch can)
     TRY(upload_plan(b, P, models[0]->d, ctrl, h_env_model));
     HIP_OK(uhc_set_lds_limit(b->lds_bytes, b->lds_bytes_fast, b->lds_bytes_big));
     TRY(alloc_state(b, models, h_env_model));
@@ -442,7 +442,7 @@ static KernelArgs wire_launch(const UhcBatch* b, const StepLaunch& L, int sticky
     K.fin = at(b->d_fin, L.fin, 1);
     K.q_next = at(b->d_lists, L.next_list, E); K.q_next_count = at(b->d_counts, L.next_count, 1);
     K.chunk = L.chunk;
-    K.order = L.use_order ? b->d_order : nullptr;  // (null with UHC_DEBUG bit 3: env order)
+    K.order = L.use_order ? b->d_order : nullptr;  // (null with UHC_DEBUG_ENV_ORDER)
     return K;
 }
 static int launch_sticky(UhcBatch* b, int mode, const double* d_action, const double* d_tbase, const int* d_active, const EvPair* ev) {
@@ -450,7 +450,7 @@ static int launch_sticky(UhcBatch* b, int mode, const double* d_action, const do
     in.n_env = b->n_env; in.n_cu = b->n_cu; in.lds_bytes_fast = b->lds_bytes_fast; in.large_first = b->large_first;
     in.fast_chunk = b->fast_chunk; in.n_substeps = b->A.c.n_substeps; in.last_tier = b->A.last_tier; set_caps(in, b->caps);
 #ifdef UHC_EXPERIMENTS
-    in.fixed_cap2 = (b->A.dbg & 2048) != 0;  // (measurement switch: a fixed cap UHC_Q2_MAX on the general tier's consumers)
+    in.fixed_cap2 = (b->A.dbg & UHC_DEBUG_EXP_FIXED_CAP2) != 0;  // (measurement switch: a fixed cap UHC_Q2_MAX on the general tier's consumers)
 #endif
     long long seen = 0;
     // tier 4's consumers: the list kernel fills their queue, so this is decided first -- before the back-off bookkeeping below, like the counts it is sized from
@@ -468,7 +468,7 @@ static int launch_sticky(UhcBatch* b, int mode, const double* d_action, const do
     if (const int* hc = newest_counts(b, &seen)) {
         // queue lengths at the end of the newest step seen, and how many of the general tier's came in during the step
         in.est2 = hc[UHC_CNT_GEN]; in.est3 = hc[UHC_CNT_BIG]; in.handed2 = std::max(0, hc[UHC_CNT_GEN] - hc[UHC_CNT_GEN_HEAD]);
-        if (b->A.dbg & 64)
+        if (b->A.dbg & UHC_DEBUG_LOG)
             fprintf(stderr, "uhc step %lld: queues %d / %d envs (%d handed on), gate waited %.1f us, gave up %d, queues_off %d\n", seen, in.est2, in.est3, in.handed2,
                     0.01 * hc[UHC_CNT_GATE_WAIT], hc[UHC_CNT_GIVE_UPS], (int)b->queues_off);
         update_back_off(b, hc[UHC_CNT_GIVE_UPS]);
@@ -484,10 +484,10 @@ static int launch_sticky(UhcBatch* b, int mode, const double* d_action, const do
         const hipStream_t st = streams[L.stream];
         const bool side = L.stream != STREAM_MAIN;
         if (side) HIP_OK(hipStreamWaitEvent(st, b->ev_fork, 0));
-        if (L.gate_started != UHC_NONE && !(b->A.dbg & 32))  // (UHC_DEBUG bit 5: no gates; bit 4: the trace of the gate that reports its wait, in the record of the last env)
+        if (L.gate_started != UHC_NONE && !(b->A.dbg & UHC_DEBUG_NO_GATE))  // (under UHC_DEBUG_TRACE: the trace of the gate that reports its wait, in the record of the last env)
             HIP_OK(uhc_launch_gate(b->d_fin + L.gate_started, L.gate_want, L.gate_waited != UHC_NONE ? b->d_counts + L.gate_waited : nullptr,
-                                   (L.gate_waited != UHC_NONE && (b->A.dbg & 16)) ? b->A.s.prof + (size_t)(b->n_env - 1) * UHC_NPROF + 16 : nullptr, st));
-        if (L.tier == 4 && (b->A.dbg & 64)) fprintf(stderr, "uhc step %lld: %d tier-4 consumers (%d env-steps went through tier 4 when last seen)\n", b->cnt_step, L.grid, in.est4);
+                                   (L.gate_waited != UHC_NONE && (b->A.dbg & UHC_DEBUG_TRACE)) ? b->A.s.prof + (size_t)(b->n_env - 1) * UHC_NPROF + UHC_TRACE_GATE : nullptr, st));
+        if (L.tier == 4 && (b->A.dbg & UHC_DEBUG_LOG)) fprintf(stderr, "uhc step %lld: %d tier-4 consumers (%d env-steps went through tier 4 when last seen)\n", b->cnt_step, L.grid, in.est4);
         const KernelArgs K = wire_launch(b, L, z.sticky_mask);
         if (side) {
             HIP_OK(uhc_launch_step(mode, L.tier, &K, d_action, d_tbase, nullptr, lds[L.tier], st));

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/uhc_amd.h"  // (UhcDebug, UhcTraceWord, UHC_PROF_WORDS)
 
 #define UHC_WAVE 64
 // capacities per env of the kernel tiers (fast / general / large / huge): constraint rows, contacts, rows between two moving bodies (kept
@@ -31,7 +32,18 @@
 #define UHC_CON_STRIDE 24
 #define UHC_MINVAL 1e-15
 #define UHC_MAXVAL 1e10
-#define UHC_NPROF 40  // int64 words per env of the stage-profile record (UHC_F_STAGE_PROF)
+#define UHC_NPROF UHC_PROF_WORDS  // int64 words per env of the stage-profile record (UHC_F_STAGE_PROF)
+// the tier trace's words by tier (UhcTraceWord, include/uhc_amd.h)
+__host__ __device__ constexpr int trace_taken(int tier) { return tier < 4 ? UHC_TRACE_TAKEN + 2 * (tier - 1) : UHC_TRACE_TAKEN4; }
+__host__ __device__ constexpr int trace_let_go(int tier) { return tier < 4 ? UHC_TRACE_LET_GO + 2 * (tier - 1) : UHC_TRACE_LET_GO4; }
+// (tier 4 hands nothing on -- hands_on<4> is 4 < last_tier, never true, and only a tier that hands on raises UHC_ST_HANDON -- but the compiler cannot see that: its
+//  instantiation carries the store, which never executes.  The word is the one the macro's old arithmetic gave it, so that the kernels' code stays what it was)
+__host__ __device__ constexpr int trace_handon_substep(int tier) { return tier < 3 ? UHC_TRACE_HANDON_SUBSTEP + (tier - 1) : tier == 3 ? UHC_TRACE_HANDON_SUBSTEP3 : UHC_TRACE_LET_GO4; }
+__host__ __device__ constexpr int trace_consumer(int tier) { return UHC_TRACE_CONSUMER + UHC_TRACE_CONSUMER_WORDS * (tier - 2); }
+static_assert(trace_taken(1) == 0 && trace_let_go(1) == 1 && trace_taken(2) == 2 && trace_let_go(2) == 3 && trace_taken(3) == 4 && trace_let_go(3) == 5, "stamps of tiers 1-3");
+static_assert(trace_handon_substep(1) == 6 && trace_handon_substep(2) == 7 && trace_handon_substep(3) == 23 && trace_handon_substep(4) == 22, "hand-on substeps (tier 4: never stored)");
+static_assert(trace_consumer(2) == 8 && trace_consumer(3) == 12 && UHC_TRACE_GATE == 16 && trace_consumer(3) + UHC_TRACE_CONSUMER_WORDS <= UHC_TRACE_GATE, "the consumers' records end below the gate's");
+static_assert(trace_taken(4) == 21 && trace_let_go(4) == 22 && UHC_TRACE_CHUNK_WAIT == 24 && UHC_TRACE_CHUNK_WAIT < UHC_PROF_WORDS, "tier 4's stamps, the chunk wait");
 
 // Sticky tiers: the words through which a step's launches find each other.  Four small int arrays of the batch -- the env queues `lists`
 // [UHC_N_LISTS][n_env], and `counts`, `cursors`, `fin` of UHC_N_WORDS ints each -- are reset by the list kernel at the head of the step
@@ -221,7 +233,7 @@ struct KernelArgs {
                    // four-wave consumers' queue, and stays there while it peaks above 3/4 of the mark (0: never; UHC_T4_ROWS)
     int truncate;  // fast kernel: drop contacts / rows beyond its capacity instead of handing the env to the general kernel
     int ball_limits;  // the model has limited ball joints: the fast tier launches its DENSE instantiation (which carries the ball-limit rows)
-    int dbg;                 // debug switches (UHC_DEBUG env var): bit 0 = working sets never merge islands, bit 1 = MPR vertices not staged in LDS, bit 2 = a handed-on env restarts its step instead of resuming at the substep, bit 3 = sticky fast tier launches in env order, bit 4 = tier trace in the stage-profile record, bit 5 = no gate before the fast tier's launch, bit 6 = log the queue lengths and the gate's wait per step, bit 7 = no box cull of the convex pairs, bit 8 (256) = the general tier's first working set is NOT filled by rank (k_as_general; A/B of DESIGN 2), bits 9 / 10 (512 / 1024) = fill 48 / 56 lanes instead of 64, bit 11 (2048) = fixed cap UHC_Q2_MAX on the general tier's consumers (plan_sticky_step, uhc_plan.cpp).  bit 12 (4096) = sticky tier 4: an env whose step ended in tier 4 starts its next step there, at the head of the tier-4 consumers' queue (uhc_tier_lists_kernel; uhc_capi.cpp launch_sticky(); measured and not the default, see uhc_step_env).  Bits 8-12 change which envs report windows / sweeps in UHC_F_REDO: measurement switches that exist only in libraries built with -DUHC_EXPERIMENTS (tools/ A/B builds) -- the shipped library compiles their reads out (UHC_EXP in uhc_physics_impl.h) and masks the bits (uhc_capi.cpp); uhc_build_flags() bit 0 tells which kind a library is
+    int dbg;                 // debug switches (UHC_DEBUG env var): enum UhcDebug, include/uhc_amd.h
     int nvp;                 // stride of a dense row (nv rounded up to 2 doubles)
     int adjdeg;              // stride of the per-model hull adjacency table (largest vertex degree over the batch's models)
     DevCtrl c;

@@ -46,7 +46,7 @@ extern __shared__ __attribute__((aligned(16))) double smem[];
 #define PROF_PASS
 #define PROF(i)
 #endif
-// Measurement switches of the solver (UHC_DEBUG bits 8-10 and 12: working-set fill, sticky tier 4) exist only in libraries built with -DUHC_EXPERIMENTS
+// Measurement switches of the solver (UHC_DEBUG_EXP_*, include/uhc_amd.h: working-set fill, sticky tier 4) exist only in libraries built with -DUHC_EXPERIMENTS
 // (tools/ A/B builds); the shipped library compiles them out -- a stray environment variable cannot change which envs report windows / sweeps
 // (uhc_build_flags() bit 0 says which kind a library is; tests/test_capi_symbols.py asserts the shipped one is not).
 #ifdef UHC_EXPERIMENTS
@@ -1016,7 +1016,7 @@ __device__ __forceinline__ int k_collision(const KernelArgs& A, const double* mb
                 // limb's bounding sphere reaches far beyond its sides; side by side (thighs, arm along the torso) the spheres overlap in
                 // every pose and the pair went through the whole portal search only to be found apart.  Conservative: a box holds its
                 // hull, and boxes further apart than the margin along an axis mean hulls further apart than the margin.
-                if (c && !(A.dbg & 128)) {
+                if (c && !(A.dbg & UHC_DEBUG_NO_BOX_CULL)) {
                     const double* B1 = mb + A.o.geom_box + 6 * g1;
                     const double* B2 = mb + A.o.geom_box + 6 * g2;
                     double c1[3], c2[3], dw[3];
@@ -2223,7 +2223,7 @@ __device__ __forceinline__ int k_as_general(const KernelArgs& A, const double* m
     int rk[NRL];
 #pragma unroll
     for (int h = 0; h < NRL; h++) rk[h] = 0;
-    if (!UHC_EXP(256)) {
+    if (!UHC_EXP(UHC_DEBUG_EXP_NO_RANK_FILL)) {
 #pragma unroll
         for (int h2 = 0; h2 < NRL; h2++) {
             const int n2 = min(UHC_WAVE, nefc - h2 * UHC_WAVE);
@@ -2239,7 +2239,7 @@ __device__ __forceinline__ int k_as_general(const KernelArgs& A, const double* m
 #pragma unroll
         for (int h = 0; h < NRL; h++) rk[h] = 1 << 20;
     }
-    const int nfill = UHC_EXP(512) ? 48 : UHC_EXP(1024) ? 56 : UHC_WS_FILL;  // (UHC_DEBUG bits 9 / 10: experiments)
+    const int nfill = UHC_EXP(UHC_DEBUG_EXP_FILL_48) ? 48 : UHC_EXP(UHC_DEBUG_EXP_FILL_56) ? 56 : UHC_WS_FILL;  // (experiments)
 #pragma unroll
     for (int h = 0; h < NRL; h++) fpos[h] = fpos[h] || (vv[h] && rk[h] < nfill);  // from here on: the first candidates
     wsync();  // (the dense rows' Delassus columns may live where the contacts were: nothing reads the contacts from here on)
@@ -2254,7 +2254,7 @@ __device__ __forceinline__ int k_as_general(const KernelArgs& A, const double* m
 #pragma unroll 1
         for (int b = 1; b < T.nbody; b++) todo |= __builtin_amdgcn_ballot_w64(isl[h] == b) ? (1ull << b) : 0ull;
     }
-    bool nomerge = (A.dbg & 1) != 0;
+    bool nomerge = (A.dbg & UHC_DEBUG_NO_MERGE) != 0;
     while (todo) {
         // ---- next group: islands are independent, but every solve pays the fixed cost of a register-resident build, so small islands
         //      share one (A is block diagonal across them by itself: rows of different trees have no common dofs).  Islands are packed
@@ -2848,14 +2848,14 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
     wsync();
 #endif
     const double* mb = A.s.model_blob + (size_t)(A.s.env_model ? A.s.env_model[env] : 0) * A.o.stride;
-    // tier trace (UHC_DEBUG bit 4, product builds; tools/tier_trace.py): when each tier took the env up and let it go (100 MHz wall clock)
+    // tier trace (UHC_DEBUG_TRACE, product builds; tools/tier_trace.py): when each tier took the env up and let it go (100 MHz wall clock)
     // and the substep of a hand-on, in the first words of the env's stage-profile record
 #ifndef UHC_STAGE_PROF
-#define TRACE(slot, v) if (MODE == 0 && (A.dbg & 16) && LANE == 0) A.s.prof[(size_t)env * UHC_NPROF + (TIER < 4 ? (slot) : 21 + ((slot) & 1))] = (long long)(v);  // (tier 4's stamps: words 21 / 22; the substep at which the large tier handed on: word 23)
+#define TRACE(word, v) if (MODE == 0 && (A.dbg & UHC_DEBUG_TRACE) && LANE == 0) A.s.prof[(size_t)env * UHC_NPROF + (word)] = (long long)(v);  // (the words by tier: trace_taken ..., uhc_device.h)
 #else
-#define TRACE(slot, v)
+#define TRACE(word, v)
 #endif
-    if (!CH || lo == 0) { TRACE(2 * (TIER - 1), wall_clock64()) }
+    if (!CH || lo == 0) { TRACE(trace_taken(TIER), wall_clock64()) }
     int fail = MODE == 0 ? A.s.fail[env] : 0;
     // A tier that finds an env too big in substep k >= 1 hands it on WITH the substeps it has done: the state at the start of substep k
     // (qpos, qvel, warm start) and that substep's controls (ctrl, applied: PD torque and residual force are already computed) are in
@@ -2998,7 +2998,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
         }
     }
     if (overflow & UHC_ST_HANDON) {  // nothing committed: the next tier takes the env over -- from the substep that did not fit, or from the same inputs
-        if (MODE == 0 && it >= 1 && it > res && !(A.dbg & 4)) {  // (UHC_DEBUG bit 2: hand on from the start of the step, for A/B measurements)
+        if (MODE == 0 && it >= 1 && it > res && !(A.dbg & UHC_DEBUG_RESTART_HANDON)) {  // (hand on from the start of the step, for A/B measurements)
             for (int i = LANE; i < T.nq; i += UHC_WAVE) A.s.qpos[(size_t)env * T.nq + i] = S[L.qpos + i];
             for (int i = LANE; i < T.nv; i += UHC_WAVE) {
                 A.s.qvel[(size_t)env * T.nv + i] = S[L.qvel + i];
@@ -3007,7 +3007,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
             }
             for (int i = LANE; i < T.nu; i += UHC_WAVE) A.s.ctrl[(size_t)env * T.nu + i] = S[L.ctrl + i];
             if (LANE == 0) A.s.resume[env] = it;
-            TRACE(TIER < 3 ? 5 + TIER : 23, it)
+            TRACE(trace_handon_substep(TIER), it)
             __threadfence();  // (the queue append below publishes the env: its state must be visible first)
         }
         if (LANE == 0) {
@@ -3025,7 +3025,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
             }
             if (TIER == 1 && MODE == 0) atomicAdd(A.s.path_stats, 1ull);
         }
-        TRACE(2 * (TIER - 1) + 1, wall_clock64())
+        TRACE(trace_let_go(TIER), wall_clock64())
         guard_check<TIER>(A, S, env, 0);
         return 1;
     }
@@ -3083,7 +3083,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
         }
         return 2;
     }
-    TRACE(2 * (TIER - 1) + 1, wall_clock64())
+    TRACE(trace_let_go(TIER), wall_clock64())
     double vmax_end = 0.0;  // largest |qvel| at the end of the step (the launch order of the next one)
     if (MODE == 0) {
         for (int i = LANE; i < T.nv; i += UHC_WAVE) vmax_end = fmax(vmax_end, fabs(S[L.qvel + i]));
@@ -3102,7 +3102,7 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
         if (TIER == 2) A.s.pend2[env] = 0;  // taken: the chained launch of this tier has nothing left to do for the env
         if (TIER >= 3) A.s.pend3[env] = 0;
         if (MODE == 0 && ran_step) {  // where the env's next step starts, and where in the fast tier's launch order (the policy: uhc_step_words.h)
-            A.s.tier[env] = next_tier(TIER, pk_nefc, pk_ncon, pk_ntwo, pk_y, pk_act, A, UHC_EXP(4096));
+            A.s.tier[env] = next_tier(TIER, pk_nefc, pk_ncon, pk_ntwo, pk_y, pk_act, A, UHC_EXP(UHC_DEBUG_EXP_STICKY_TIER4));
             A.s.cost[env] = launch_cost(pk_nefc, pk_ncon, pk_ntwo, pk_y, vmax_end, A);
         }
         if (redo_written(TIER, overflow)) A.s.redo[env] = redo_word(TIER, overflow, swept);
@@ -3190,7 +3190,7 @@ __device__ __forceinline__ int chunk_wait(const KernelArgs& A, const int env, co
         __builtin_amdgcn_s_sleep(32);
     }
 #ifndef UHC_STAGE_PROF
-    if (A.dbg & 16) A.s.prof[(size_t)env * UHC_NPROF + 24] += (long long)(wall_clock64() - t_in);  // tier trace: ticks the env's chunks spent waiting (the tool clears the record per step)
+    if (A.dbg & UHC_DEBUG_TRACE) A.s.prof[(size_t)env * UHC_NPROF + UHC_TRACE_CHUNK_WAIT] += (long long)(wall_clock64() - t_in);  // tier trace: ticks the env's chunks spent waiting (the tool clears the record per step)
 #endif
     return r;
 }
@@ -3265,9 +3265,8 @@ __global__ void __launch_bounds__(UHC_QUEUE_THREADS) uhc_step_queue_kernel(Kerne
     if (threadIdx.x >= UHC_WAVE) { mpr_helper<TIER>(A, smem); return; }
 #endif
     if (A.started && LANE == 0) atomicAdd(A.started, 1);  // resident: holds its LDS from here on
-    // (tier trace, UHC_DEBUG bit 4: the consumer's own record -- entry, first env claimed, exit, envs processed -- in words 8 .. 11 (general
-    //  tier) / 12 .. 15 (large tier) of the stage-profile record of env blockIdx.x)
-    long long* tr = (TIER < 4 && (A.dbg & 16) && (int)blockIdx.x < A.n_env) ? A.s.prof + (size_t)blockIdx.x * UHC_NPROF + 8 + 4 * (TIER - 2) : nullptr;
+    // (tier trace: the consumer's own record -- entry, first env claimed, exit, envs processed -- at trace_consumer(TIER) of the stage-profile record of env blockIdx.x)
+    long long* tr = (TIER < 4 && (A.dbg & UHC_DEBUG_TRACE) && (int)blockIdx.x < A.n_env) ? A.s.prof + (size_t)blockIdx.x * UHC_NPROF + trace_consumer(TIER) : nullptr;
     if (tr && LANE == 0) { tr[0] = (long long)wall_clock64(); tr[1] = 0; tr[3] = 0; }
     int role = 0;
     for (;;) {

@@ -28,9 +28,9 @@ BatchKnobs read_knobs() {
     // move by a few doubles; capacities and tiers stay as they are.  MPR's vertex staging, which runs across three regions on purpose, is off.
     k.guard = is("UHC_GUARD_LDS", '2') ? 2 : is("UHC_GUARD_LDS", '1') ? 1 : 0;  // (2: one "guard" sits ON qpos of the fast tier -- the report must fire: tests/test_gpu_poison.py)
     if (const char* dbg = getenv("UHC_DEBUG")) k.dbg = atoi(dbg);
-    if (k.guard) k.dbg |= 2;
+    if (k.guard) k.dbg |= UHC_DEBUG_NO_VSTAGE;
 #ifndef UHC_EXPERIMENTS
-    k.dbg &= ~0x1f00;  // bits 8-12 (working-set fill, consumer cap, sticky tier 4) are measurement switches of tools/ builds: the shipped library does not read them
+    k.dbg &= ~UHC_DEBUG_EXP_MASK;  // (working-set fill, consumer cap, sticky tier 4: measurement switches of tools/ builds: the shipped library does not read them)
 #endif
     if (const char* m = getenv("UHC_TIER_MARKS")) sscanf(m, "%d,%d,%d,%d,%d,%d,%d,%d", k.marks + UHC_MARK_UP2_ROWS, k.marks + UHC_MARK_UP2_CON, k.marks + UHC_MARK_UP2_TWO, k.marks + UHC_MARK_DN1_ROWS, k.marks + UHC_MARK_DN1_CON, k.marks + UHC_MARK_DN1_TWO, k.marks + UHC_MARK_UP3_8THS, k.marks + UHC_MARK_DN2_8THS);
     // UHC_FAST_DENSE = "KiB,dense rows[,contacts]": the dense fast tier's LDS budget, body-body row slots and contact capacity (experiments)
@@ -370,7 +370,7 @@ static void fast_layout(Carver& cv, const UhcModelDesc& d, int n_env, const Batc
     if (ycap < need1) ycap = need1;
     if (ycap < 8 * YS) ycap = 8 * YS;
     A.cf.ycap = ycap;
-    A.cf.vstage = ((A.dbg & 2) == 0 && T.ncpair > 0 && 3 * d.nmeshvert <= A.cf.ndense * A.nvp + (dcol_alias ? 0 : A.cf.ndense * UHC_WAVE) + ycap) ? F.dense : -1;  // dense, (dcol,) Y are contiguous
+    A.cf.vstage = ((A.dbg & UHC_DEBUG_NO_VSTAGE) == 0 && T.ncpair > 0 && 3 * d.nmeshvert <= A.cf.ndense * A.nvp + (dcol_alias ? 0 : A.cf.ndense * UHC_WAVE) + ycap) ? F.dense : -1;  // dense, (dcol,) Y are contiguous
     cv.off += ycap;
     cv.end_guard();
     F.rowR = F.rowAref = F.rowB = F.rowF = F.rowDa = F.rowW = F.rowY = F.dsc = F.Y;  // unused by the fast kernel
@@ -412,7 +412,7 @@ static bool rows_layout(Carver& cv, const UhcModelDesc& d, const KernelArgs& A, 
     if (!full_y && ycap < 64 * 18) return false;  // too little left for rows: not worth a tier of its own
     if (ycap < cv.end1 - cv.off) ycap = cv.end1 - cv.off;     // (the region also holds the dynamics temporaries of phase 1)
     cp.ycap = ycap & ~1;
-    cp.vstage = ((A.dbg & 2) == 0 && T.ncpair > 0 && 3 * d.nmeshvert <= cp.ndense * A.nvp + cp.ndense * 4 + cp.ycap) ? F.dense : -1;
+    cp.vstage = ((A.dbg & UHC_DEBUG_NO_VSTAGE) == 0 && T.ncpair > 0 && 3 * d.nmeshvert <= cp.ndense * A.nvp + cp.ndense * 4 + cp.ycap) ? F.dense : -1;
     cv.off += cp.ycap;
     cv.end_guard();
     F.total = cv.off;
@@ -444,7 +444,7 @@ static bool huge_layout(Carver& cv, const UhcModelDesc& d, const KernelArgs& A, 
     F.Y = F.dense = F.H;  // (never addressed in this tier: the rows live in gY / gD)
     cp.ycap = maxefc * YS + 8;
     // MPR's hull vertices: staged where the Hessian will be (nothing of it exists during the collision pass) when they fit
-    cp.vstage = ((A.dbg & 2) == 0 && T.ncpair > 0 && 3 * d.nmeshvert <= (nv * (nv + 1)) / 2) ? F.H : -1;
+    cp.vstage = ((A.dbg & UHC_DEBUG_NO_VSTAGE) == 0 && T.ncpair > 0 && 3 * d.nmeshvert <= (nv * (nv + 1)) / 2) ? F.H : -1;
     if (cv.off < cv.end1) cv.off = cv.end1;  // (the region also holds the dynamics temporaries of phase 1)
     cv.end_guard();
     F.total = cv.off;
@@ -488,7 +488,7 @@ static int upper_tiers(Carver* cv, const UhcModelDesc& d, const BatchKnobs& knob
             if (score > best) { best = score; best_me = me; best_mc = mc; }
         }
         ok4 = best_me > 0 && huge_layout(cv[3], d, A, A.lx, A.cx, best_me, best_mc);
-        if (ok4 && (A.dbg & 64)) fprintf(stderr, "uhc tier 4: %d rows / %d contacts / %d body-body rows, %d B of LDS\n", A.cx.maxefc, A.cx.maxcon, A.cx.ndense, A.lx.total * 8);
+        if (ok4 && (A.dbg & UHC_DEBUG_LOG)) fprintf(stderr, "uhc tier 4: %d rows / %d contacts / %d body-body rows, %d B of LDS\n", A.cx.maxefc, A.cx.maxcon, A.cx.ndense, A.lx.total * 8);
         if (ok4) {
             A.last_tier = 4;
             P.lds_bytes_big = std::max(P.lds_bytes_big, (size_t)A.lx.total * sizeof(double));
@@ -672,7 +672,7 @@ int default_fast_chunk(int knob, int n_substeps, int n_env, int n_cu, size_t lds
 // general tier had a queue (est2_then: the consumers need the large tier's beside them, which run whenever the general tier's do), a few persistent workgroups
 // wait on a queue of their own beside everything else, and the large tier's consumers append what they find too big instead of leaving it for the chained
 // launch at the very end of the step -- where a 10 ms env-step of one env used to be added to every step in which any env needed tier 4 (configs[4]: 64 k ->
-// 42 k env-steps/s when tier 4 came in).  Envs that START in tier 4 (UHC_DEBUG bit 12) are put at the head of that queue by the list kernel.
+// 42 k env-steps/s when tier 4 came in).  Envs that START in tier 4 (UHC_DEBUG_EXP_STICKY_TIER4) are put at the head of that queue by the list kernel.
 bool sticky_launch4(int last_tier, int est4, int est2_then, bool queues_off) { return last_tier == 4 && est4 > 0 && est2_then > 0 && !queues_off; }
 
 StickySizes plan_sticky_step(const StickyInputs& in, bool launch4) {

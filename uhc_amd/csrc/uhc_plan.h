@@ -9,7 +9,7 @@
 
 // the UHC_* environment variables of batch creation, parsed and range-checked (read_knobs is the one place of the host code that reads the environment)
 struct BatchKnobs : QueueCaps {    // (the caps: UHC_Q2_DIV, UHC_Q2_WAIT, UHC_Q2_MAX, UHC_Q3_MAX, UHC_Q4_MAX)
-    int dbg = 0;                    // UHC_DEBUG (KernelArgs::dbg; bits 8-12 only in -DUHC_EXPERIMENTS builds)
+    int dbg = 0;                    // UHC_DEBUG (KernelArgs::dbg: enum UhcDebug; UHC_DEBUG_EXP_* only in -DUHC_EXPERIMENTS builds)
     int marks[UHC_N_MARKS] = {64, 16, -1, 56, 14, 10, 8, 7};  // UHC_TIER_MARKS "a,b,c,d,e,f,g,h" in UhcMark's order (the body-body up mark < 0: the body-body marks follow the fast layout)
     int fast_dense_got = 0, fast_dense_kib = 0, fast_dense_rows = 0, fast_dense_con = 0;  // UHC_FAST_DENSE "KiB,dense rows[,contacts]": fields read, their values
     bool fast_dcol_own = false;     // UHC_FAST_DCOL_OWN=1
@@ -61,7 +61,7 @@ struct StickyInputs {
     int last_tier;
     bool queues_off;       // no waiting consumers (back-off after a consumer gave up)
     int q2_div, q2_wait_min, q2_max, q3_max, q4_max;  // QueueCaps, member for member (set_caps): the test probes fill this struct by position AND set these by name
-    bool fixed_cap2;       // measurement switch (UHC_DEBUG bit 11 of -DUHC_EXPERIMENTS builds): a fixed cap UHC_Q2_MAX on the general tier's consumers
+    bool fixed_cap2;       // measurement switch (UHC_DEBUG_EXP_FIXED_CAP2 of -DUHC_EXPERIMENTS builds): a fixed cap UHC_Q2_MAX on the general tier's consumers
     int fast_chunk;        // BatchKnobs::fast_chunk (0: the default), and the control step's substeps (0: the fast tier's launch is not chunked)
     int n_substeps;
 };

@@ -110,7 +110,7 @@ static_assert(sizeof(KernelArgs::marks) == UHC_N_MARKS * sizeof(int), "one mark 
 // longer fits costs that tier's work so far, and the step then ends a whole general- (or large-) tier env-step after the moment
 // of the hand-on -- with a thousand envs some env does that every step, and every step lasts fast + general + large.  It comes
 // down again only well below the mark (hysteresis).  The marks are the batch's (KernelArgs::marks, UHC_TIER_MARKS).
-// tier: the tier that finished the step; pk_*: the step's peaks over its substeps -- rows, contacts, body-body rows, packed Yhat entries, force-carrying rows.  sticky4: the measurement switch UHC_DEBUG bit 12 (read by the kernel, behind UHC_EXP)
+// tier: the tier that finished the step; pk_*: the step's peaks over its substeps -- rows, contacts, body-body rows, packed Yhat entries, force-carrying rows.  sticky4: the measurement switch UHC_DEBUG_EXP_STICKY_TIER4 (read by the kernel, behind UHC_EXP)
 UHC_WORDS_FN int next_tier(const int tier, const int pk_nefc, const int pk_ncon, const int pk_ntwo, const int pk_y, const int pk_act, const KernelArgs& A, const bool sticky4) {
     const int* mk = A.marks;  // up2: rows, contacts, body-body rows | dn1: the same | up3, dn2: eighths of the general tier's capacities
     const bool up2 = pk_nefc > mk[UHC_MARK_UP2_ROWS] || pk_ncon > mk[UHC_MARK_UP2_CON] || pk_ntwo > mk[UHC_MARK_UP2_TWO];   // of 64 rows / 16 contacts / 12 body-body rows
@@ -128,7 +128,7 @@ UHC_WORDS_FN int next_tier(const int tier, const int pk_nefc, const int pk_ncon,
     else next = !dn2 ? 3 : (dn1 ? 1 : 2);
     // an env that needed tier 4 (beyond the large tier's capacities, or more force-carrying rows than its working sets finish) starts its next
     // step THERE: at the head of the queue of tier 4's consumers (uhc_capi.cpp) instead of an abandoned large-tier attempt first.  It comes down with room to spare: 3/4 of the large tier's capacities and <= 48 rows with a force.
-    // OPT-IN (UHC_DEBUG bit 12): measured on the random-policy ball-joint rollouts it LOSES -- configs[4] 41.6 k -> 27.1 k env-steps/s: the envs that
+    // OPT-IN (UHC_DEBUG_EXP_STICKY_TIER4): measured on the random-policy ball-joint rollouts it LOSES -- configs[4] 41.6 k -> 27.1 k env-steps/s: the envs that
     // reach tier 4 there are diverging ones that reset within two or three steps, a reset env then runs its first step in tier 4 too, and a whole step of
     // primal solves costs more than the large-tier attempt it saves -- so by default such an env starts its next step in the large tier.
     // Heavy envs go STRAIGHT to tier 4 (round 6): the four-wave Newton iteration on the primal costs the same whatever the number of rows, while a

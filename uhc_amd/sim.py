@@ -10,6 +10,9 @@ import numpy as np
 import torch
 
 from ._capi import UhcCtrlDesc, UhcEnvDesc, model_desc
+from ._capi import (DEBUG_ENV_ORDER, DEBUG_EXP_FILL_48, DEBUG_EXP_FILL_56, DEBUG_EXP_FIXED_CAP2, DEBUG_EXP_MASK, DEBUG_EXP_NO_RANK_FILL, DEBUG_EXP_STICKY_TIER4,  # noqa: F401
+                    DEBUG_LOG, DEBUG_NO_BOX_CULL, DEBUG_NO_GATE, DEBUG_NO_MERGE, DEBUG_NO_VSTAGE, DEBUG_RESTART_HANDON, DEBUG_TRACE, PROF_WORDS, TRACE_CHUNK_WAIT,
+                    TRACE_CONSUMER, TRACE_CONSUMER_WORDS, TRACE_GATE, TRACE_HANDON_SUBSTEP, TRACE_HANDON_SUBSTEP3, TRACE_LET_GO, TRACE_LET_GO4, TRACE_TAKEN, TRACE_TAKEN4)
 from ._capi import (REDO_DROPPED, REDO_GENERAL, REDO_LARGE, REDO_PRIMAL, REDO_PRIMAL_CAP, REDO_SWEPT, REDO_SWEPT_SUBSTEP0, REDO_SWEPT_SUBSTEPS,  # noqa: F401 (re-exported next to F_*)
                     REDO_WHY_FRICTION, REDO_WHY_NOCONV, REDO_WHY_PIVOT, REDO_WINDOWED, WHY_CANDIDATES, WHY_CONTACTS, WHY_DENSE_SLOTS, WHY_FAST_SHIFT, WHY_FIELD,
                     WHY_GENERAL_SHIFT, WHY_LARGE_SHIFT, WHY_ROW_STORAGE, WHY_ROWS, WHY_SOLVER, WHY_SUBSTEP_SHIFT)
@@ -110,7 +113,7 @@ class SimBatch:
         check(self.L.uhc_batch_field(self._b, f, C.byref(p), C.byref(n)))
         per = n.value // self.n_env
         if f == F_STAGE_PROF:
-            t = torch.as_tensor(_DevView(p.value, (self.n_env, 40), "<i8", self), device=self.device)
+            t = torch.as_tensor(_DevView(p.value, (self.n_env, PROF_WORDS), "<i8", self), device=self.device)
         elif f in _INT_FIELDS:
             t = torch.as_tensor(_DevView(p.value, (self.n_env,), "<i4", self), device=self.device)
         else:
