@@ -29,7 +29,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define UHC_ABI_VERSION 11  /* 11: uhc_expert_frames (the clip bank's frame records computed on the device); 10: uhc_build_flags; 9: UHC_F_REDO bits 29 / 30 (tier 4), swept-substep bits 8 .. 28; uhc_rollout_record counts int64 [7] */
+#define UHC_ABI_VERSION 11  /* 11: uhc_expert_frames (the clip bank's frame records computed on the device) -- uhc_eval_record / uhc_eval_metrics came later and are purely additive: still 11; 10: uhc_build_flags; 9: UHC_F_REDO bits 29 / 30 (tier 4), swept-substep bits 8 .. 28; uhc_rollout_record counts int64 [7] */
 
 /* joint / geom type codes (MuJoCo numbering) */
 enum { UHC_JNT_FREE = 0, UHC_JNT_BALL = 1, UHC_JNT_SLIDE = 2, UHC_JNT_HINGE = 3 };
@@ -459,6 +459,44 @@ int32_t uhc_filter_apply(void* stream, const double* d_x, int32_t n_rows, int32_
 int32_t uhc_expert_frames(void* stream, int32_t n_body, const int32_t* h_parent, const int32_t* h_ee_body, const double* d_body_pos,
                           const double* d_body_ipos, int32_t n_models, const double* d_qpos, int64_t n_frames, const int32_t* d_clip_start,
                           const int32_t* d_clip_model, int32_t n_clips, const double* d_root_quat_record, double dt, double* d_frames);
+
+/* ------------------------------------------------------------------ evaluation on the device: trajectory record and imitation metrics
+ * Replaces the host half of eval_seq (uhc/agents/agent_copycat.py:438-494: per control step, copies of qpos / xpos / the expert frame / done / reward /
+ * percent and Python lists per clip) and compute_metrics (uhc/smpllib/smpl_eval.py:66-126).  Free functions like uhc_rollout_* and uhc_expert_frames:
+ * `stream` is a hipStream_t (NULL = the default stream); every argument is checked before the first HIP call; n_env == 0 succeeds and launches nothing;
+ * reductions have a fixed order and no floating-point atomics (two runs are bit-identical); no counter or index, whatever it holds, sends a read or a
+ * write outside the arrays.  (Purely additive: UHC_ABI_VERSION stays 11.)
+ *
+ * The record belongs to the CALLER (zeroed before an episode batch):
+ *   d_rows, d_steps int32 [n_env]      rows / rewards written so far
+ *   d_pred_qpos [n_env][row_cap][nqh]  the humanoid's part of qpos
+ *   d_pred_jpos [n_env][row_cap][72]   bodies 1 .. 24 of xpos
+ *   d_gt_frame int64 [n_env][row_cap]  bank frame of the row: d_clip0[e] + min(t, d_len[e] - 1)
+ *   d_rewards [n_env][row_cap]
+ *   d_fail_safe int32 [n_env], d_percent [n_env], d_tele int32 [n_env], d_overflow int32 [1]
+ * uhc_eval_record takes one snapshot for the envs with d_alive[e] != 0 (the mask handed to uhc_env_step):
+ *   phase 0 (before the step): appends a row.
+ *   phase 1 (after it): d_rewards[e][d_steps[e]++] = d_reward[e]; where d_done[e], appends a row with the same t, then -- fail_safe != 0 and
+ *           d_percent_in[e] != 1 -- sets d_fail_safe[e] = d_tele[e] = 1 (the caller teleports the env to the expert pose and the episode goes on), or else
+ *           clears d_alive[e] and writes d_percent[e].  d_tele is rewritten for EVERY env by every phase-1 call (0 where nothing is to teleport).
+ * A row that does not fit row_cap is counted in d_overflow and not written.
+ *   n_body 24; nq, nbody: row widths of d_qpos [n_env][nq] and d_xpos [n_env][nbody][3] (body 0 = the world; objects behind the humanoid);
+ *   nqh: 7 .. nq.  d_done, d_reward, d_percent_in may be NULL in phase 0. */
+int32_t uhc_eval_record(void* stream, int32_t phase, int32_t n_env, int32_t n_body, int32_t nq, int32_t nqh, int32_t nbody, int32_t row_cap, int32_t t,
+                        int32_t fail_safe, const double* d_qpos, const double* d_xpos, const int64_t* d_clip0, const int32_t* d_len,
+                        const int32_t* d_done, const double* d_reward, const double* d_percent_in, int32_t* d_alive, int32_t* d_rows,
+                        int32_t* d_steps, double* d_pred_qpos, double* d_pred_jpos, int64_t* d_gt_frame, double* d_rewards, int32_t* d_fail_safe,
+                        double* d_percent, int32_t* d_tele, int32_t* d_overflow);
+/* compute_metrics for every env of a record against the bank d_frames [n_frames][UHC_FRAME_STRIDE] (gt root pose at UHC_FR_QPOS, gt joints at UHC_FR_WBPOS).
+ *   d_row_metrics [n_env][row_cap][6]: root_dist (divided by the env's row count), vel_dist, accel_dist, mpjpe_g, pa_mpjpe, mpjpe, in mm.  An env with T rows
+ *                  gets T rows, T - 1 for vel_dist, T - 2 for accel_dist (numpy's lengths); every other slot is left untouched.
+ *   d_clip_means [n_env][6]: the means over those rows; over no row: NaN (np.mean of an empty array).
+ *   d_bad int32 [1]: set by the call to the number of read d_gt_frame entries outside [0, n_frames).  Such an entry is not followed: every output that
+ *                  would read it (the row's six, and the velocity / acceleration of the one or two rows before it) is NaN.
+ *   h_bad (HOST, may be NULL): when given, the call waits for the stream and stores d_bad's count there; otherwise it is asynchronous like the rest. */
+int32_t uhc_eval_metrics(void* stream, int32_t n_env, int32_t n_body, int32_t nqh, int32_t row_cap, const int32_t* d_rows, const double* d_pred_qpos,
+                         const double* d_pred_jpos, const int64_t* d_gt_frame, const double* d_frames, int64_t n_frames, double* d_row_metrics,
+                         double* d_clip_means, int32_t* d_bad, int32_t* h_bad);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

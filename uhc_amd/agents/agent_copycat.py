@@ -413,6 +413,8 @@ def _eval_seqs(self, take_keys, loader):
     ev.set_rfc_rate(self.env.rfc_rate)
     out = {}
     frames, starts = ev.env._bank[0], ev.env._bank[1].cpu().numpy()
+    if getattr(cfg, "eval_build", "host") == "device":
+        return _eval_seqs_device(self, ev, take_keys, loader, n)
     for c0 in range(0, len(take_keys), n):
         keys = take_keys[c0:c0 + n]
         m = len(keys)
@@ -488,6 +490,100 @@ def _eval_seqs(self, take_keys, loader):
             res["reward"] = np.array(rec["reward"][e])
             res["percent"], res["fail_safe"] = percent[e], bool(fail_safe[e])
             res.update(compute_metrics(res, None))
+            out[k] = res
+    return out
+
+
+def _eval_seqs_device(self, ev, take_keys, loader, n):
+    """eval_seqs with cfg.eval_build == "device": the same chunks, assign / reset, filter calls and simulation calls as the host loop above, but the
+    trajectory is appended on the device (uhc_eval_record) and scored there (uhc_eval_metrics).  The step loop reads nothing back when cfg.fail_safe is
+    off -- it runs max(lens) steps, then looks at the number of envs still alive, and goes on in short blocks while there are any --; with cfg.fail_safe
+    it reads the list of envs to teleport once per step.  One copy per chunk brings rows, rewards and metrics to the host, where the per-clip dicts of
+    the host path are cut from it."""
+    from .. import eval_ops as EO
+    from .. import sim as S
+    cfg = self.cfg
+    dev = ev.device
+    out = {}
+    frames, starts = ev.env._bank[0], ev.env._bank[1].cpu().numpy()
+    ql = ev.qpos_lim
+    nm = len(EO.METRICS)
+    for c0 in range(0, len(take_keys), n):
+        keys = take_keys[c0:c0 + n]
+        m = len(keys)
+        ids = np.arange(m)
+        lens = np.array([loader.get_sample_len_from_key(k) for k in keys])
+        ev.assign(ids, keys, np.zeros(m, dtype=int), lens)
+        ev.reset(ids)
+        # the reference filters the reset observation with update=True (agent_copycat.py:445-446); kept
+        state = self.running_state(ev.obs[:m].to(self.dtype)) if self.running_state is not None else ev.obs[:m].to(self.dtype)
+        if m < n:
+            state = torch.cat([state, state.new_zeros(n - m, state.shape[1])])
+        active = torch.zeros(n, dtype=torch.int32, device=dev)  # the step's mask AND the record's: uhc_eval_record clears the entries of finished episodes
+        active[:m] = 1
+        clip0 = torch.zeros(n, dtype=torch.int64, device=dev)
+        clip0[:m] = torch.from_numpy(np.array([starts[ev._clip_index[k]] for k in keys], dtype=np.int64)).to(dev)
+        lens_d = torch.ones(n, dtype=torch.int32, device=dev)
+        lens_d[:m] = torch.from_numpy(lens.astype(np.int32)).to(dev)
+        block = int(lens.max())
+        rec = EO.Record(n, 2 * block + 2, ql, dev)
+        qpos_f, xpos_f, pct_f = ev.sim.field(S.F_QPOS), ev.sim.field(S.F_XPOS), ev.env.field(S.E_PERCENT)
+        t = 0
+
+        def step():
+            nonlocal state
+            EO.record(rec, 0, t, qpos_f, xpos_f, clip0, lens_d, active)
+            action = self.policy_net.select_action(self.trans_policy(state), True).to(torch.float64).contiguous()
+            ev.step(action, active)
+            EO.record(rec, 1, t, qpos_f, xpos_f, clip0, lens_d, active, done=ev.done, reward=ev.reward, percent=pct_f, fail_safe=cfg.fail_safe)
+            if cfg.fail_safe:
+                ti = rec.tele.nonzero()[:, 0]  # (the one read of a fail-safe step: how many envs teleport)
+                if ti.numel():  # teleport to the expert state and keep going (humanoid_im.py:902-905)
+                    fr = frames[clip0[ti] + torch.minimum(ev.cur_t[ti], lens_d[ti] - 1).to(torch.int64)]
+                    qp, qv = S.expert_pose_of_frames(fr, ev.use_quat)
+                    if ev.num_obj:  # the objects stay where they are
+                        qp = torch.cat([qp, qpos_f[ti, ql:]], 1)
+                        qv = torch.cat([qv, ev.sim.field(S.F_QVEL)[ti, ev.qvel_lim:]], 1)
+                    ev.sim.set_state(qp.contiguous(), qv.contiguous(), ti.to(torch.int32))
+            state = self.running_state(ev.obs.to(self.dtype), update=False) if self.running_state is not None else ev.obs.to(self.dtype)
+
+        while True:
+            for _ in range(block):
+                step()
+                t += 1
+            if int(active.sum().item()) == 0:
+                break
+            block = 16
+
+        row_metrics, _, bad = EO.metrics(rec, frames)
+        # ---- one copy: [per-env words | overflow, bad | every valid row: pred, pred_jpos, gt, gt_jpos, metrics | every reward]
+        ar = torch.arange(rec.row_cap, device=dev)[None]
+        rmask, smask = ar < rec.rows[:, None], ar < rec.steps[:, None]
+        gi = rec.gt_frame[rmask].clamp(0, frames.shape[0] - 1)
+        g = frames[gi]
+        rows_d = torch.cat([rec.pred_qpos[rmask], rec.pred_jpos[rmask], g[:, 0:76], g[:, 151:223], row_metrics[rmask]], 1)
+        words = torch.stack([rec.rows.double(), rec.steps.double(), rec.fail_safe.double(), rec.percent], 1)
+        flat = torch.cat([words.reshape(-1), rec.overflow.double(), bad.double(), rows_d.reshape(-1), rec.rewards[smask]]).cpu().numpy()
+        words = flat[:4 * n].reshape(n, 4)
+        overflow, n_bad = int(flat[4 * n]), int(flat[4 * n + 1])
+        if overflow:
+            raise RuntimeError(f"eval_seqs: {overflow} trajectory rows did not fit the record (row_cap {rec.row_cap})")
+        if n_bad:
+            raise RuntimeError(f"eval_seqs: {n_bad} recorded expert frame indices lie outside the clip bank")
+        n_rows, n_steps = words[:, 0].astype(int), words[:, 1].astype(int)
+        W = ql + 72 + 76 + 72 + nm
+        rows_h = flat[4 * n + 2:4 * n + 2 + n_rows.sum() * W].reshape(-1, W)
+        rew_h = flat[4 * n + 2 + n_rows.sum() * W:]
+        r0 = np.concatenate([[0], np.cumsum(n_rows)])
+        s0 = np.concatenate([[0], np.cumsum(n_steps)])
+        for e, k in enumerate(keys):
+            rw, T = rows_h[r0[e]:r0[e + 1]], n_rows[e]
+            res = {"gt": rw[:, ql + 72:ql + 148].copy(), "pred": rw[:, :ql].copy(), "gt_jpos": rw[:, ql + 148:ql + 220].copy(), "pred_jpos": rw[:, ql:ql + 72].copy()}
+            res["reward"] = rew_h[s0[e]:s0[e + 1]].copy()
+            res["percent"], res["fail_safe"] = words[e, 3], bool(words[e, 2])
+            for i, name in enumerate(EO.METRICS):  # numpy's lengths: T rows, T - 1 for the velocity, T - 2 for the acceleration
+                res[name] = rw[:max(T - (1 if name == "vel_dist" else 2 if name == "accel_dist" else 0), 0), ql + 220 + i].copy()
+            res["succ"] = np.array([(not res["fail_safe"]) and res["percent"] == 1])
             out[k] = res
     return out
 

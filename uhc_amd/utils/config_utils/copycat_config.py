@@ -98,6 +98,11 @@ class Config(Base_Config):
         self.bank_build = g("bank_build", "host")
         if self.bank_build not in ("host", "device"):
             raise ValueError(f"bank_build: 'host' or 'device', got {self.bank_build!r}")
+        # where eval_seqs keeps and scores an episode's trajectory: "host" -- per control step, copies to the host and Python lists, compute_metrics in numpy --,
+        # "device" -- uhc_eval_record appends on the device (no device -> host read in the step loop), uhc_eval_metrics scores, one copy per chunk of clips
+        self.eval_build = g("eval_build", "host")
+        if self.eval_build not in ("host", "device"):
+            raise ValueError(f"eval_build: 'host' or 'device', got {self.eval_build!r}")
         self.ppo_dtype = g("ppo_dtype", "float64")
         # data-parallel gradient exchange: the dtype on the wire.  float32 (default): SURVEY 8e's 32 MB per optimisation epoch; the local
         # gradient means travel scaled by the rank's sample count and are divided by the global count in the parameters' own float64, so the
