@@ -460,6 +460,23 @@ int32_t uhc_expert_frames(void* stream, int32_t n_body, const int32_t* h_parent,
                           const double* d_body_ipos, int32_t n_models, const double* d_qpos, int64_t n_frames, const int32_t* d_clip_start,
                           const int32_t* d_clip_model, int32_t n_clips, const double* d_root_quat_record, double dt, double* d_frames);
 
+/* ------------------------------------------------------------------ AMASS poses -> qpos rows on the device
+ * The step in front of uhc_expert_frames: smpl_to_qpose (uhc/smpllib/smpl_mujoco.py:543-607) as ONE launch over (frame, joint).  Per joint: rotation vector
+ * -> quaternion (scipy's from_rotvec, no canonical sign) -> intrinsic ZYX Euler angles by scipy's quaternion algorithm, gimbal-lock branches included (X = 0
+ * at lock); the root of the 76-wide row keeps a quaternion, formed through the rotation matrix with the reference converter's branch rule.  Free function
+ * like uhc_expert_frames: `stream` is a hipStream_t (NULL = the default stream); every argument is checked before the first HIP call; n_frames == 0 succeeds
+ * and launches nothing; no atomics (two runs are bit-identical); whatever the clip tables hold, no read or write leaves the arrays -- a d_clip_start that does
+ * not ascend can only name the wrong clip, a d_clip_model outside 0 .. n_models - 1 reads as 0.  (Purely additive: UHC_ABI_VERSION stays 11.)
+ *   n_joint 24; h_smpl_to_model [24] (HOST): the SMPL joint model slot m takes -- a permutation of 0 .. 23 with entry 0 = 0;
+ *   d_root_offset [n_models][3]: each body shape's body_pos[1], added to the root position (NULL: count_offset=False);
+ *   d_pose_aa [n_frames][72]; d_trans [n_frames][3] (NULL: (0, 0, 0.91437225) for every frame);
+ *   d_clip_start int32 [n_clips], d_clip_model int32 [n_clips] (NULL: model 0 for every clip): which body shape's offset a frame gets;
+ *   d_qpos [n_frames][76]: position, root quaternion (w, x, y, z), 23 x (Z, Y, X); d_qpos_quat [n_frames][99]: position, 24 x (w, x, y, z).  Either may be
+ *   NULL, not both; both are 16-byte aligned. */
+int32_t uhc_smpl_qpos(void* stream, int32_t n_joint, const int32_t* h_smpl_to_model, const double* d_root_offset, int32_t n_models,
+                      const double* d_pose_aa, const double* d_trans, int64_t n_frames, const int32_t* d_clip_start, const int32_t* d_clip_model,
+                      int32_t n_clips, double* d_qpos, double* d_qpos_quat);
+
 /* ------------------------------------------------------------------ evaluation on the device: trajectory record and imitation metrics
  * Replaces the host half of eval_seq (uhc/agents/agent_copycat.py:438-494: per control step, copies of qpos / xpos / the expert frame / done / reward /
  * percent and Python lists per clip) and compute_metrics (uhc/smpllib/smpl_eval.py:66-126).  Free functions like uhc_rollout_* and uhc_expert_frames:

@@ -20,7 +20,7 @@ SYMBOLS = [
     "uhc_env_create", "uhc_env_free", "uhc_env_obs_dim", "uhc_env_field", "uhc_env_set_bank", "uhc_env_assign",
     "uhc_env_reset", "uhc_env_step", "uhc_env_set_next", "uhc_env_auto_reset", "uhc_env_set_clip_models", "uhc_env_set_end_reward", "uhc_env_set_obj_pose",
     "uhc_rollout_act", "uhc_rollout_record", "uhc_filter_scratch_doubles", "uhc_filter_push", "uhc_filter_apply",
-    "uhc_expert_frames", "uhc_eval_record", "uhc_eval_metrics",
+    "uhc_expert_frames", "uhc_eval_record", "uhc_eval_metrics", "uhc_smpl_qpos",
 ]
 
 
@@ -93,6 +93,9 @@ def lib():
         L.uhc_eval_record.argtypes = [P] + [I] * 9 + [P] * 18
         L.uhc_eval_metrics.argtypes = [P, I, I, I, I, P, P, P, P, P, C.c_int64, P, P, P, C.POINTER(I)]
         L.uhc_eval_record.restype = L.uhc_eval_metrics.restype = I
+    if hasattr(L, "uhc_smpl_qpos"):  # (additive within ABI 11)
+        L.uhc_smpl_qpos.argtypes = [P, I, C.POINTER(I), P, I, P, P, C.c_int64, P, P, I, P, P]
+        L.uhc_smpl_qpos.restype = I
     _lib = L
     return L
 

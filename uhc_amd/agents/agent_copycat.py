@@ -95,7 +95,7 @@ class AgentCopycat(AgentPPO):
                 model, self._shape_models = models[0], models[1:]
         self.env = VecHumanoidEnv(self.cfg, n_env=self.cfg.n_env, device=dev_index, mode="train", model=model, shape_models=self._shape_models, objects=self._objects)
         self.env.set_clip_bank_from_loader(self.data_loader, clip_model={k: v for k, v in self._clip_model.items() if k in set(self.data_loader.data_keys)} if self._clip_model else None,
-                                          build=getattr(self.cfg, "bank_build", "host"))
+                                          build=getattr(self.cfg, "bank_build", "host"), convert=getattr(self.cfg, "bank_convert", "host"))
 
     def setup_policy(self):
         cfg, env = self.cfg, self.env
@@ -407,7 +407,8 @@ def _eval_seqs(self, take_keys, loader):
         ev = VecHumanoidEnv(cfg, n_env=n, device=self.env.device.index or 0, mode="test", model=self.env.body_model, shape_models=self.env.body_models[1:],
                             objects=self.env.objects)
         cm = getattr(self, "_clip_model", None)  # every clip is evaluated on its own body, as it is trained (a clip the map does not name: body 0)
-        ev.set_clip_bank_from_loader(loader, clip_model={k: cm.get(k, 0) for k in loader.data_keys} if cm else None, build=getattr(cfg, "bank_build", "host"))
+        ev.set_clip_bank_from_loader(loader, clip_model={k: cm.get(k, 0) for k in loader.data_keys} if cm else None, build=getattr(cfg, "bank_build", "host"),
+                                     convert=getattr(cfg, "bank_convert", "host"))
         self._eval_envs = getattr(self, "_eval_envs", {})
         self._eval_envs[(loader.name, n)] = ev
     ev.set_rfc_rate(self.env.rfc_rate)

@@ -158,15 +158,21 @@ class VecHumanoidEnv:
             raise ValueError(f"the env carries {self.num_obj} objects: every clip needs obj_pose of shape (T, {7 * self.num_obj})")
         return op
 
-    def set_clip_bank(self, clips: dict, clip_model: dict = None, build: str = "host"):
+    def set_clip_bank(self, clips: dict, clip_model: dict = None, build: str = "host", convert: str = "host"):
         """clips: {key: sample dict with pose_aa/trans/beta/gender (+ obj_pose when the env carries objects) of the WHOLE clip}.  Builds the
         HBM bank once.  clip_model: {key: index into [model] + shape_models}: the body shape every episode of that clip runs on.
         build: "host" -- qpos_fk and the packing of the frame records clip by clip on the host, the records uploaded; "device" -- only the
-        AMASS -> qpos conversion on the host, ONE upload of the qpos rows and ONE uhc_expert_frames launch for the whole bank."""
+        AMASS -> qpos conversion on the host, ONE upload of the qpos rows and ONE uhc_expert_frames launch for the whole bank.
+        convert (build="device" only): "host" -- that conversion is smpl_to_qpose, clip by clip; "device" -- the raw pose and trans arrays of all
+        clips are uploaded once, ONE uhc_smpl_qpos launch writes the qpos rows and they feed uhc_expert_frames where they lie."""
         if build not in ("host", "device"):
             raise ValueError(f"set_clip_bank: build must be 'host' or 'device', got {build!r}")
+        if convert not in ("host", "device"):
+            raise ValueError(f"set_clip_bank: convert must be 'host' or 'device', got {convert!r}")
+        if convert == "device" and build != "device":
+            raise ValueError("set_clip_bank: convert='device' needs build='device' (the host build reads its qpos rows on the host)")
         if build == "device":
-            return self._set_clip_bank_device(clips, clip_model)
+            return self._set_clip_bank_device(clips, clip_model, convert)
         frames, starts, betas, lens, objs = [], [], [], [], []
         n = 0
         self.clip_keys = list(clips.keys())
@@ -199,22 +205,29 @@ class VecHumanoidEnv:
         beta = np.concatenate([beta, np.zeros(16 - beta.shape[0])]) if beta.shape[0] < 16 else beta[:16]
         return np.r_[beta, float(np.asarray(c["gender"]).reshape(-1)[0])]
 
-    def _set_clip_bank_device(self, clips, clip_model):
-        """set_clip_bank(build="device"): the host keeps smpl_to_qpose (scipy's Euler branch rules); everything behind it -- Humanoid.qpos_fk and
-        pack_expert_frames -- is uhc_expert_frames on the env's stream, on each clip's own body shape."""
+    def _set_clip_bank_device(self, clips, clip_model, convert="host"):
+        """set_clip_bank(build="device"): Humanoid.qpos_fk and pack_expert_frames are uhc_expert_frames on the env's stream, on each clip's own body
+        shape.  convert="host": the host keeps smpl_to_qpose (scipy itself); convert="device": that too is a launch (uhc_smpl_qpos, scipy's
+        formulas and branch rules restated) and no qpos row visits the host."""
         self.clip_keys = list(clips.keys())
         cm = [int(clip_model[k]) if clip_model else 0 for k in self.clip_keys]
-        rows, quats, starts, betas, lens, objs = [], [], [], [], [], []
+        rows, quats, trs, starts, betas, lens, objs = [], [], [], [], [], [], []
         n = 0
+        smpl_model, count_offset = self.cc_cfg.robot_cfg.get("model", "smpl"), self.cc_cfg.robot_cfg.get("mesh", True)
+        if convert == "device" and smpl_model != "smpl":
+            raise NotImplementedError("only the options the copycat path uses are built (SURVEY.md 8f-4)")  # (as smpl_to_qpose refuses it)
         for k, mi in zip(self.clip_keys, cm):
             c = clips[k]
             kin = self.body_models[mi]
-            kw = dict(pose=c["pose_aa"], trans=np.asarray(c["trans"]).squeeze(), model=self.cc_cfg.robot_cfg.get("model", "smpl"),
-                      count_offset=self.cc_cfg.robot_cfg.get("mesh", True))
-            q = np.asarray(smpl_to_qpose(mj_model=kin, **kw), dtype=np.float64)
+            if convert == "device":  # the raw arrays: what smpl_to_qpose would reshape them to
+                q = np.asarray(c["pose_aa"], dtype=np.float64).reshape(-1, 72)
+                trs.append(np.asarray(c["trans"], dtype=np.float64).squeeze().reshape(q.shape[0], 3))
+            else:
+                kw = dict(pose=c["pose_aa"], trans=np.asarray(c["trans"]).squeeze(), model=smpl_model, count_offset=count_offset)
+                q = np.asarray(smpl_to_qpose(mj_model=kin, **kw), dtype=np.float64)
+                if self.use_quat:  # the record's root quaternion comes out of the second conversion (expert_features)
+                    quats.append(np.asarray(smpl_to_qpose(mj_model=kin, use_quat=True, **kw), dtype=np.float64)[:, 3:7])
             rows.append(q)
-            if self.use_quat:  # the record's root quaternion comes out of the second conversion (expert_features)
-                quats.append(np.asarray(smpl_to_qpose(mj_model=kin, use_quat=True, **kw), dtype=np.float64)[:, 3:7])
             if self.num_obj:
                 objs.append(self._clip_obj_pose(c, q.shape[0]))
             starts.append(n)
@@ -228,17 +241,23 @@ class VecHumanoidEnv:
                 self._humanoids[i] = Humanoid(model=m)
         hums = [self._humanoids[i] for i in range(len(self.body_models))]
         with torch.cuda.device(self.device):
-            frames = S.expert_frames_device(torch.from_numpy(np.concatenate(rows)), starts, hums,
-                                            clip_model=cm if clip_model else None,
-                                            root_quat_record=torch.from_numpy(np.concatenate(quats)) if self.use_quat else None, device=self.device)
+            if convert == "device":
+                got = S.smpl_qpos_device(torch.from_numpy(np.concatenate(rows)), torch.from_numpy(np.concatenate(trs)), starts, list(self.body_models),
+                                         clip_model=cm if clip_model else None, count_offset=count_offset,
+                                         want=("qpos", "qpos_quat") if self.use_quat else ("qpos",), device=self.device)
+                qpos, record = got[0], got[1][:, 3:7] if self.use_quat else None  # (the 99-wide rows' root quaternion IS the record's)
+            else:
+                qpos = torch.from_numpy(np.concatenate(rows))
+                record = torch.from_numpy(np.concatenate(quats)) if self.use_quat else None
+            frames = S.expert_frames_device(qpos, starts, hums, clip_model=cm if clip_model else None, root_quat_record=record, device=self.device)
         self.env.set_bank(frames, torch.tensor(starts, dtype=torch.int32), torch.from_numpy(np.stack(betas)))
         self.env.set_obj_pose(torch.from_numpy(np.concatenate(objs)) if self.num_obj else None)
         self.env.set_clip_models(torch.tensor(cm, dtype=torch.int32) if clip_model else None)
 
-    def set_clip_bank_from_loader(self, data_loader, clip_model=None, build="host"):
+    def set_clip_bank_from_loader(self, data_loader, clip_model=None, build="host", convert="host"):
         clips = {k: dict(pose_aa=data_loader.data["pose_aa"][k], trans=data_loader.data["trans"][k], beta=data_loader.data["beta"][k],
                          gender=data_loader.data["gender"][k], obj_pose=data_loader.data.get("obj_pose", {}).get(k)) for k in data_loader.data_keys}
-        self.set_clip_bank(clips, clip_model=clip_model, build=build)
+        self.set_clip_bank(clips, clip_model=clip_model, build=build, convert=convert)
 
     def _window_len(self, fr_start, fr_end):
         n = np.asarray(fr_end) - np.asarray(fr_start)
@@ -421,7 +440,8 @@ class HumanoidEnv(MujocoEnv):
         self.expert = dict(expert_data)
         self.expert["meta"] = {"cyclic": False, "seq_name": expert_data["seq_name"]}
         self.expert.update(self.vec.expert_features(expert_data))
-        self.vec.set_clip_bank({expert_data["seq_name"]: expert_data}, build=getattr(self.cc_cfg, "bank_build", "host"))  # (self.expert above stays the host's: the getters read it)
+        self.vec.set_clip_bank({expert_data["seq_name"]: expert_data}, build=getattr(self.cc_cfg, "bank_build", "host"),
+                               convert=getattr(self.cc_cfg, "bank_convert", "host"))  # (self.expert above stays the host's: the getters read it)
         self.vec.assign([0], [expert_data["seq_name"]], [0], [self.expert["len"]])
 
     def reset_model(self):  # (MujocoEnv.reset calls it: mujoco_env.py:95-104)

@@ -280,6 +280,62 @@ def expert_frames_device(qpos, clip_start, humanoids, clip_model=None, root_quat
     return out
 
 
+def smpl_qpos_device(pose_aa, trans, clip_start, models, clip_model=None, count_offset: bool = True, want=("qpos",), device=None):
+    """AMASS axis-angle poses -> qpos rows on the device (uhc_smpl_qpos): what `smpl_to_qpose(clip, model)`, clip by clip, gives on the host, from
+    ONE upload of the raw arrays and ONE launch on torch's current stream.
+      pose_aa (n_frames, 72) and trans (n_frames, 3) or None: the clips one after another (numpy or torch, host or device); clip_start: first row of
+      every clip; models: one compiled `Model` (or a list of them, same body order) per body shape -- their root offsets (body_pos[1]) are uploaded
+      once and added to the root position when count_offset --, clip_model: which of them each clip is converted for (None: the first for every
+      clip); want: ("qpos",), ("qpos_quat",) or both -- the hinge humanoid's 76-wide rows, the ball-joint humanoid's 99-wide rows.
+    Returns the float64 device tensors in the order of `want`; they go into `expert_frames_device` as they are."""
+    from .smpllib.smpl_mujoco import smpl_to_model_table
+    if not torch.cuda.is_available():
+        raise RuntimeError("uhc_amd.sim.smpl_qpos_device needs an MI355X (torch.cuda unavailable); there is no CPU fallback")
+    ms = list(models) if isinstance(models, (list, tuple)) else [models]
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in ("qpos", "qpos_quat") for w in want):
+        raise ValueError(f"smpl_qpos_device: want names 'qpos' and / or 'qpos_quat', got {want!r}")
+    if device is None:
+        device = pose_aa.device if isinstance(pose_aa, torch.Tensor) and pose_aa.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    tables = [smpl_to_model_table(m) for m in ms]
+    if any(t != tables[0] for t in tables[1:]):
+        raise ValueError("smpl_qpos_device: every body shape must share the first one's body order")
+    s2m = np.ascontiguousarray(tables[0], dtype=np.int32)
+    if s2m.shape != (24,):
+        raise ValueError(f"smpl_qpos_device: the model carries {s2m.size} of the 24 SMPL bodies")
+    cs = np.asarray(clip_start.cpu() if isinstance(clip_start, torch.Tensor) else clip_start, dtype=np.int64).reshape(-1)
+    pose = torch.as_tensor(pose_aa)
+    n_frames = int(pose.shape[0])
+    if pose.ndim < 2 or pose.numel() != n_frames * 72:
+        raise ValueError(f"smpl_qpos_device: pose_aa must be (n_frames, 72) or (n_frames, 24, 3), got {tuple(pose.shape)}")
+    pose = pose.reshape(n_frames, 72)
+    if trans is not None:
+        trans = torch.as_tensor(trans)
+        if tuple(trans.shape) != (n_frames, 3):
+            raise ValueError(f"smpl_qpos_device: trans must be ({n_frames}, 3), got {tuple(trans.shape)}")
+    if cs.size == 0 or cs[0] != 0 or np.any(np.diff(cs) <= 0) or (n_frames and cs[-1] >= n_frames):
+        raise ValueError("smpl_qpos_device: clip_start must ascend strictly from 0 and stay below n_frames")
+    cm = None
+    if clip_model is not None:
+        cm = np.asarray(clip_model.cpu() if isinstance(clip_model, torch.Tensor) else clip_model, dtype=np.int64).reshape(-1)
+        if cm.shape != cs.shape or cm.min() < 0 or cm.max() >= len(ms):
+            raise ValueError(f"smpl_qpos_device: clip_model must name one of the {len(ms)} body shapes for each of the {cs.size} clips")
+    widths = dict(qpos=76, qpos_quat=99)
+    with torch.cuda.device(device):  # (the temporaries below are freed in stream order: the launch is on torch's current stream)
+        out = {w: torch.empty((n_frames, widths[w]), dtype=torch.float64, device=device) for w in want}
+        if n_frames:
+            off = torch.from_numpy(np.stack([np.asarray(m.body_pos, dtype=np.float64)[1] for m in ms])).to(device).contiguous() if count_offset else None
+            p = pose.to(device, torch.float64).contiguous()
+            t = None if trans is None else trans.to(device, torch.float64).contiguous()
+            d_cs = torch.from_numpy(cs.astype(np.int32)).to(device)
+            d_cm = None if cm is None else torch.from_numpy(cm.astype(np.int32)).to(device)
+            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+            check(lib().uhc_smpl_qpos(C.c_void_p(torch.cuda.current_stream(device).cuda_stream), 24, s2m.ctypes.data_as(C.POINTER(C.c_int32)), ptr(off), len(ms),
+                                      ptr(p), ptr(t), n_frames, ptr(d_cs), ptr(d_cm), int(cs.size), ptr(out.get("qpos")), ptr(out.get("qpos_quat"))))
+    return tuple(out[w] for w in want)
+
+
 class EnvBatch:
     """Device env layer (uhc_env_* of the C-ABI) on top of a SimBatch."""
 

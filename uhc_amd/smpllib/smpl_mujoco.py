@@ -150,6 +150,11 @@ def rotation_matrix_to_quaternion(R):
     return q
 
 
+def smpl_to_model_table(mj_model):
+    """-> the SMPL joint that each of the model's bodies (in its depth-first qpos order) takes: `smpl_2_mujoco` of the reference's smpl_to_qpose"""
+    return [SMPL_BONE_ORDER_NAMES.index(q) for q in get_body_qposaddr(mj_model).keys() if q in SMPL_BONE_ORDER_NAMES]
+
+
 def smpl_to_qpose(pose, mj_model, trans=None, normalize=False, random_root=False, count_offset=True, use_quat=False,
                   euler_order="ZYX", model="smpl"):
     """AMASS axis-angle pose (B,72) [+ trans (B,3)] -> qpos (B,76) of the hinge humanoid
@@ -166,9 +171,8 @@ def smpl_to_qpose(pose, mj_model, trans=None, normalize=False, random_root=False
         trans = np.zeros((B, 3))
         trans[:, 2] = 0.91437225
     trans = np.asarray(trans, dtype=np.float64).reshape(B, 3)
-    names = SMPL_BONE_ORDER_NAMES
-    smpl_2_mujoco = [names.index(q) for q in get_body_qposaddr(mj_model).keys() if q in names]
-    rot = sRot.from_rotvec(pose.reshape(-1, 3))
+    smpl_2_mujoco = smpl_to_model_table(mj_model)
+    rot =sRot.from_rotvec(pose.reshape(-1, 3))
     if use_quat:
         quat = rot.as_quat()[:, [3, 0, 1, 2]].reshape(B, 24, 4)[:, smpl_2_mujoco, :].reshape(B, 96)
         qpos = np.concatenate((trans, quat), axis=1)
@@ -181,6 +185,22 @@ def smpl_to_qpose(pose, mj_model, trans=None, normalize=False, random_root=False
     if count_offset:
         qpos[:, :3] = trans + np.asarray(mj_model.body_pos)[1]
     return qpos
+
+
+def smpl_to_qpose_device(pose, mj_model, trans=None, normalize=False, random_root=False, count_offset=True, use_quat=False,
+                         euler_order="ZYX", model="smpl"):
+    """`smpl_to_qpose` of ONE clip computed on the device (uhc_smpl_qpos, uhc_amd.sim.smpl_qpos_device): same arguments, the result a float64 device
+    tensor -- (B, 76), or (B, 99) with use_quat.  What the host function refuses is refused here in the same way."""
+    from ..sim import smpl_qpos_device
+    if normalize or random_root or model != "smpl":
+        raise NotImplementedError("only the options the copycat path uses are built (SURVEY.md 8f-4)")
+    if euler_order != "ZYX":
+        raise NotImplementedError("the device conversion is the intrinsic ZYX one (the hinge humanoid's joint order)")
+    import torch
+    pose = torch.as_tensor(pose).reshape(-1, 72)
+    if trans is not None:
+        trans = torch.as_tensor(trans).reshape(pose.shape[0], 3)
+    return smpl_qpos_device(pose, trans, [0], mj_model, count_offset=count_offset, want=("qpos_quat",) if use_quat else ("qpos",))[0]
 
 
 def qpos_to_smpl(qpos, mj_model, smpl_model="smpl"):

@@ -98,6 +98,11 @@ class Config(Base_Config):
         self.bank_build = g("bank_build", "host")
         if self.bank_build not in ("host", "device"):
             raise ValueError(f"bank_build: 'host' or 'device', got {self.bank_build!r}")
+        # where the AMASS -> qpos conversion in front of a device-built bank runs (set_clip_bank(convert=)): "host" -- smpl_to_qpose clip by clip --, "device"
+        # -- the raw pose / trans arrays uploaded, one uhc_smpl_qpos launch; it needs bank_build "device" (set_clip_bank refuses the combination otherwise)
+        self.bank_convert = g("bank_convert", "host")
+        if self.bank_convert not in ("host", "device"):
+            raise ValueError(f"bank_convert: 'host' or 'device', got {self.bank_convert!r}")
         # where eval_seqs keeps and scores an episode's trajectory: "host" -- per control step, copies to the host and Python lists, compute_metrics in numpy --,
         # "device" -- uhc_eval_record appends on the device (no device -> host read in the step loop), uhc_eval_metrics scores, one copy per chunk of clips
         self.eval_build = g("eval_build", "host")
