@@ -226,6 +226,7 @@ def test_layout_invariants(probe, cls, n_env, knobs):
         for (a0, a1, ka), (b0, b1, kb) in zip(spans, spans[1:]):
             assert a1 <= b0, f"tier {t}: {ka} [{a0}, {a1}) overlaps {kb} [{b0}, {b1})"
         assert total * 8 <= 160 * KIB
+        assert 2 * regs["rowMisc"][1] >= 256  # before the rows are enumerated the region is the collision stage's candidate list: CAND_CAP = 256 ints (uhc_physics_impl.h)
         vs, huge = W[cp + "vstage"], t == 3 and W["last_tier"] == 4
         assert vs == -1 or vs == W[lp + ("H" if huge else "dense")]  # the dense rows (+ Yhat behind them) / tier 4: where the Hessian will be
         if guard is not None:

@@ -49,43 +49,6 @@ __device__ __forceinline__ CcdSup sup_sel(bool c, const CcdSup& a, const CcdSup&
     return r;
 }
 
-// one convex hull posed in the world: rotation (row major), position, vertex range of the model blob
-struct CcdHull { double R[9]; V3 p; int voff, vn; };  // voff: offset (doubles) of the hull's first vertex in the vertex array
-
-// hull vertex with the largest projection on `dir` (first maximum wins), in the world, pushed out by hm = margin / 2 (+ the radius of a ROUNDED hull -- a
-// sphere is one core vertex, a capsule the two ends of its segment: include/uhc_amd.h) along dir
-__device__ __forceinline__ V3 hull_support(const double* __restrict__ VB, const CcdHull& H, const V3& dir, double hm) {
-    const double* vert = VB + H.voff;
-    const double lx = H.R[0] * dir.x + H.R[3] * dir.y + H.R[6] * dir.z;  // R^T dir
-    const double ly = H.R[1] * dir.x + H.R[4] * dir.y + H.R[7] * dir.z;
-    const double lz = H.R[2] * dir.x + H.R[5] * dir.y + H.R[8] * dir.z;
-    double bd = -1e300, bx = 0, by = 0, bz = 0;
-    // four vertices per trip: their twelve loads are issued together (the vertices sit in L2 / L1, a load costs hundreds of cycles and a
-    // one-vertex loop would pay that per vertex); the tail repeats the last vertex, which a strict `>` never selects again
-    const int last = H.vn - 1;
-    for (int v = 0; v < H.vn; v += 4) {
-        double c[4][3];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int i = 3 * min(v + k, last);
-            c[k][0] = vert[i]; c[k][1] = vert[i + 1]; c[k][2] = vert[i + 2];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const double s = lx * c[k][0] + ly * c[k][1] + lz * c[k][2];
-            if (s > bd) { bd = s; bx = c[k][0]; by = c[k][1]; bz = c[k][2]; }
-        }
-    }
-    return v3((H.R[0] * bx + H.R[1] * by + H.R[2] * bz) + (H.p.x + dir.x * hm), (H.R[3] * bx + H.R[4] * by + H.R[5] * bz) + (H.p.y + dir.y * hm),
-              (H.R[6] * bx + H.R[7] * by + H.R[8] * bz) + (H.p.z + dir.z * hm));
-}
-__device__ __forceinline__ CcdSup ccd_support(const double* __restrict__ VB, const CcdHull& H1, const CcdHull& H2, const V3& dir, double hm1, double hm2) {
-    CcdSup s;
-    const V3 v1 = hull_support(VB, H1, dir, hm1), v2 = hull_support(VB, H2, neg(dir), hm2);
-    s.v = v1 - v2;
-    s.s = v1 + v2;
-    return s;
-}
 __device__ __forceinline__ V3 portal_dir(const CcdSup& p1, const CcdSup& p2, const CcdSup& p3) {
     return vnorm(vcross(p2.v - p1.v, p3.v - p1.v));
 }
@@ -149,81 +112,20 @@ __device__ __forceinline__ V3 find_pos(const CcdSup& p0, const CcdSup& p1, const
     return v3(a.x * inv * 0.5, a.y * inv * 0.5, a.z * inv * 0.5);
 }
 
-// true: the hulls (each inflated by hm = margin / 2 + its radius) penetrate; depth, dir (from hull 1 to hull 2, zero if undefined) and pos are set.
-// c1, c2: the hulls' centres (MuJoCo: geom_xpos = the mesh's centre of mass).
-__device__ __forceinline__ bool mpr_penetration(const double* __restrict__ VB, const CcdHull& H1, const CcdHull& H2, const V3& c1, const V3& c2, double hm1, double hm2, double& depth,
-                                                V3& dir, V3& pos) {
-    CcdSup p0, p1, p2, p3, v4;
-    double dt;
-    // ---- discoverPortal
-    p0.s = c1 + c2; p0.v = c1 - c2;
-    if (ccd_eq(p0.v.x, 0) && ccd_eq(p0.v.y, 0) && ccd_eq(p0.v.z, 0)) p0.v.x += UHC_CCD_EPS * 10;
-    dir = vnorm(neg(p0.v));
-    p1 = ccd_support(VB, H1, H2, dir, hm1, hm2);
-    dt = vdot(p1.v, dir);
-    if (ccd_zero(dt) || dt < 0) return false;
-    dir = vcross(p0.v, p1.v);
-    if (ccd_zero(vdot(dir, dir))) {
-        if (ccd_eq(p1.v.x, 0) && ccd_eq(p1.v.y, 0) && ccd_eq(p1.v.z, 0)) { depth = 0; dir = v3(0, 0, 0); }   // origin on v1: touching
-        else { depth = sqrt(vdot(p1.v, p1.v)); dir = vnorm(p1.v); }                                             // origin on the segment v0-v1
-        pos = v3(0.5 * p1.s.x, 0.5 * p1.s.y, 0.5 * p1.s.z);
-        return true;
-    }
-    dir = vnorm(dir);
-    p2 = ccd_support(VB, H1, H2, dir, hm1, hm2);
-    dt = vdot(p2.v, dir);
-    if (ccd_zero(dt) || dt < 0) return false;
-    dir = vnorm(vcross(p1.v - p0.v, p2.v - p0.v));
-    if (vdot(dir, p0.v) > 0) { const CcdSup t = p1; p1 = p2; p2 = t; dir = neg(dir); }
-    for (;;) {
-        v4 = ccd_support(VB, H1, H2, dir, hm1, hm2);
-        dt = vdot(v4.v, dir);
-        if (ccd_zero(dt) || dt < 0) return false;
-        bool cont = false;
-        dt = vdot(vcross(p1.v, v4.v), p0.v);
-        if (dt < 0 && !ccd_zero(dt)) { p2 = v4; cont = true; }
-        if (!cont) {
-            dt = vdot(vcross(v4.v, p2.v), p0.v);
-            if (dt < 0 && !ccd_zero(dt)) { p1 = v4; cont = true; }
-        }
-        if (!cont) { p3 = v4; break; }
-        dir = vnorm(vcross(p1.v - p0.v, p2.v - p0.v));
-    }
-    // ---- refinePortal
-    for (;;) {
-        dir = portal_dir(p1, p2, p3);
-        dt = vdot(dir, p1.v);
-        if (ccd_zero(dt) || dt > 0) break;  // the portal encapsulates the origin
-        v4 = ccd_support(VB, H1, H2, dir, hm1, hm2);
-        dt = vdot(v4.v, dir);
-        if (!(ccd_zero(dt) || dt > 0) || portal_reach_tolerance(p1, p2, p3, v4, dir)) return false;
-        expand_portal(p0, p1, p2, p3, v4);
-    }
-    // ---- findPenetr
-    for (int it = 0;; it++) {
-        dir = portal_dir(p1, p2, p3);
-        v4 = ccd_support(VB, H1, H2, dir, hm1, hm2);
-        if (portal_reach_tolerance(p1, p2, p3, v4, dir) || it > UHC_MPR_MAXIT) {
-            V3 pd;
-            depth = sqrt(point_tri_dist2(p1.v, p2.v, p3.v, pd));
-            if (ccd_zero(pd.x) && ccd_zero(pd.y) && ccd_zero(pd.z)) pd = dir;
-            dir = vnorm(pd);
-            pos = find_pos(p0, p1, p2, p3);
-            return true;
-        }
-        expand_portal(p0, p1, p2, p3, v4);
-    }
-}
-
-// ------------------------------------------------------------------ the same refinement, supports computed by the whole wave
+// ------------------------------------------------------------------ the refinement, supports computed by the whole wave
+// (The form with one pair per lane walking its own two hulls, described above, is gone from this file: nothing called it any more and it had no UHC_MPR_MAXSUP
+// bound.  The serial statement of the algorithm is the CPU restatement's mpr_penetration, which the tests check this file against: true = the hulls, each inflated by hm = margin / 2 +
+// its radius, penetrate; depth, dir from hull 1 to hull 2 (zero if undefined) and pos; c1, c2 the hulls' centres -- MuJoCo: geom_xpos = the mesh's centre of mass.)
 // Lane = candidate pair for the PORTAL LOGIC (short, branchy, serial: lanes diverge freely), but the support function -- the only wide
 // operation and, with one pair per lane walking its own two hulls, ~85 % of the pass: 64 lanes reading 24-byte vertices at unrelated LDS
 // addresses meet ~7-way bank conflicts, ~115 cycles per vertex and lane -- is taken out of the lanes: the refinement runs in ROUNDS.
 // In a round every live pair asks for one support point (a direction); the wave then serves the requests one pair at a time with
 // lane = hull vertex (one coalesced, conflict-free read of <= 64 vertices per hull, dot product, DPP arg-max, lowest lane among equal
 // maxima = the scan's "first maximum wins"), hands the point to the pair's lane, and all lanes advance their own state machine to the
-// next request.  Same arithmetic as mpr_penetration, same portal, same result bits; the cost of a round is ~300 cycles per live pair
-// instead of ~11 000 for the slowest lane's two hull walks.
+// next request.  The CPU restatement's mpr_penetration again: same portal, same branches, the support scan's "first maximum wins" (the device contracts the projections
+// into fused multiply-adds, the CPU restatement does not: where that could part them is what tests/mpr_cases.py's ties are for); the cost of a round is ~300 cycles per live
+// pair instead of ~11 000 for the slowest lane's two hull walks.  The forms below -- mpr_wave on vertices in LDS or in global memory, mpr_wave_mw<true / false> --
+// are held to the CPU restatement and, bit for bit, to each other by tests/test_gpu_mpr_edges.py.
 enum { MPR_DONE = 0, MPR_D1, MPR_D2, MPR_D3, MPR_REFINE, MPR_PEN };
 struct MprLane {     // one candidate pair (valid in lanes whose `st` is not MPR_DONE at entry)
     int b1, b2;      // bodies of the two hulls (poses are read from LDS: xmat, xpos)
@@ -243,7 +145,8 @@ __device__ __forceinline__ double wave_max_f64(double v) {
     return fmax(fmax(bcast(v, 0), bcast(v, 16)), fmax(bcast(v, 32), bcast(v, 48)));
 }
 // support point of one hull for the pair owned by lane p (all arguments wave-uniform): the hull vertex with the largest projection on
-// dir (first maximum), in the world, pushed out by hm (margin / 2 + the hull's radius) along dir -- bit for bit hull_support's value
+// dir (first maximum: the lowest vertex index among equal projections, as the CPU restatement's serial scan keeps it), in the world, pushed out by hm (margin / 2 + the hull's
+// radius -- a sphere is one core vertex, a capsule the two ends of its segment: include/uhc_amd.h) along dir
 __device__ __forceinline__ V3 hull_support_wave(const double* __restrict__ VB, const double* __restrict__ R, const double* __restrict__ P, int voff, int vn, const V3& dir,
                                                 double hm) {
     const double lx = R[0] * dir.x + R[3] * dir.y + R[6] * dir.z;  // R^T dir
