@@ -406,6 +406,53 @@ int32_t uhc_env_reset(UhcEnv* e, const int32_t* d_env_ids, int32_t n, const doub
  * cur_t += 1, termination, reward, next observation */
 int32_t uhc_env_step(UhcEnv* e, const double* d_action, const int32_t* d_active);
 
+/* ------------------------------------------------------------------ live targets: each env imitates a stream of frames appended while it runs
+ * The per-env, per-step form of uhc_expert_frames (below): a kinematic policy, a pose estimator or a teleoperation source emits the next target pose every
+ * control step (the reference's uhc/envs/humanoid_kin_v1.py puts a frozen copycat policy under such a source), and uhc_env_live_push turns that qpos row into
+ * the frame record the env kernels read -- no host FK, no upload, no uhc_env_set_bank.  (Purely additive: UHC_ABI_VERSION stays 11.)
+ *
+ * uhc_env_live_begin  allocates a live bank [n_env][cap][UHC_FRAME_STRIDE] OWNED BY THE ENV and installs it as the env's clip bank: clip i is env i's
+ *                     stream, clip_start[i] = i cap.  Memory: n_env x cap x 4 672 B for the bank (1 024 envs x cap 512: 2.45 GB) + n_env x (76 + 17) x 8 B
+ *                     + 2 n_models x 576 B.  n_body, h_parent, h_ee_body, d_body_pos, d_body_ipos [n_models][24][3], dt: as in uhc_expert_frames; the two
+ *                     device tables are COPIED (nothing stays borrowed).  d_beta [n_env][17] or NULL (zeros): what has_shape observations append.
+ *                     n_models must be the batch's model count; the per-env model selector is the batch's own (uhc_env_set_clip_models is switched off).
+ *                     Refused: cap < 2, n_body != 24, a parent table or end effector uhc_expert_frames refuses, dt not > 0, another n_models, an env
+ *                     created with num_obj > 0.  A second call with cap <= the allocated one reuses the memory and clears every stream.
+ *                     Every slot starts as zeros and every env's window as frame 0 of its own stream: a reset or step before the first push reads zeros.
+ * uhc_env_live_push   ONE launch on the batch's stream; no allocation, no host synchronisation, no host read: it can be captured into a graph.
+ *                     d_env_ids int32 [n], d_qpos [n][76] (rows as uhc_expert_frames'), d_root_quat_record [n][4] or NULL (written into the record's
+ *                     qpos[3:7] instead of d_qpos' quaternion, which kinematics and velocities keep reading), d_restart int32 [n] or NULL, d_model int32
+ *                     [n] or NULL.  Row r, env = d_env_ids[r]:
+ *                       env outside [0, n_env): the row is ignored; no read or write goes through the index.
+ *                       d_restart[r] != 0: the row becomes frame 0 of a NEW stream, with the one-frame-clip record (zero qvel, bangvel); the stream's length
+ *                         is 1, its lowest root height the row's, dropped = 0; d_model[r] (outside 0 .. n_models - 1: 0) becomes the env's model.
+ *                       otherwise the row is appended at L = the stream's length: L == 0 (no stream) or L == cap: dropped[env] += 1, nothing else is
+ *                         written.  Else slot L gets the record of the pair (previous row, row); when L == 1, frame 0's qvel and bangvel are overwritten
+ *                         with this record's (cat(qvel[0:1], qvel)): the stream's records ARE uhc_expert_frames' of the same rows, bit for bit.
+ *                       Offsets come from the env's current model.  cur_t, done, the observation and the simulation state are not touched: after pushing the
+ *                       head of a stream the caller resets with uhc_env_reset(ids).
+ *                     Each env may appear at most ONCE per call (the caller's duty): a duplicate may lose a row, it cannot reach outside the arrays.
+ *                     n == 0 succeeds and launches nothing.
+ * uhc_env_live_view   device pointers: d_frames [n_env][cap][UHC_FRAME_STRIDE], d_len int32 [n_env], d_dropped int32 [n_env]; any may be NULL.
+ * uhc_env_live_end    leaves the env WITHOUT a bank (the live memory stays the env's, for the next live_begin, until uhc_env_free); uhc_env_set_bank
+ *                     while live ends live mode the same way and installs the caller's bank.
+ * In live mode uhc_env_assign, uhc_env_set_next, uhc_env_auto_reset, uhc_env_set_clip_models and uhc_env_set_obj_pose return an error that says so: a
+ * stream has no window to assign or queue; a done env is restarted with push(restart) + uhc_env_reset.
+ *
+ * What the env kernels make of a stream (they clamp every expert read to the stream's length - 1; step number t reads frame t + 1 for the PD target and
+ * the reward, frame t + 2 (+ k skip) for the next observation):
+ *   - with frames 0 .. t + 2 pushed before uhc_env_step number t, target, reward, termination and observation are exactly those of a clip;
+ *   - with fewer, the newest frame stands in for the missing ones;
+ *   - `end` is raised when cur_t >= len - 1 + env_expert_trail_steps -- the stream has run dry -- or at env_episode_len;
+ *   - `percent` is cur_t / (len - 1) with the length at that moment;
+ *   - observation v3 looks fut_frames skip frames ahead and sees the newest frame for whatever is not there yet. */
+int32_t uhc_env_live_begin(UhcEnv* e, int32_t cap, int32_t n_body, const int32_t* h_parent, const int32_t* h_ee_body, const double* d_body_pos,
+                           const double* d_body_ipos, int32_t n_models, double dt, const double* d_beta);
+int32_t uhc_env_live_push(UhcEnv* e, const int32_t* d_env_ids, int32_t n, const double* d_qpos, const double* d_root_quat_record,
+                          const int32_t* d_restart, const int32_t* d_model);
+int32_t uhc_env_live_view(UhcEnv* e, double** d_frames, int32_t** d_len, int32_t** d_dropped, int32_t* cap);
+int32_t uhc_env_live_end(UhcEnv* e);
+
 /* ------------------------------------------------------------------ rollout bookkeeping (one control step of the sampling loop)
  * The reference's sample_worker (uhc/khrylib/rl/agents/agent.py:60-100) does, per env step on the host: running_state(state),
  * select_action, memory.push, reward / mask bookkeeping.  Batched on the device these are launch-latency bound (~80 framework launches

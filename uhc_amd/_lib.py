@@ -21,6 +21,7 @@ SYMBOLS = [
     "uhc_env_reset", "uhc_env_step", "uhc_env_set_next", "uhc_env_auto_reset", "uhc_env_set_clip_models", "uhc_env_set_end_reward", "uhc_env_set_obj_pose",
     "uhc_rollout_act", "uhc_rollout_record", "uhc_filter_scratch_doubles", "uhc_filter_push", "uhc_filter_apply",
     "uhc_expert_frames", "uhc_eval_record", "uhc_eval_metrics", "uhc_smpl_qpos",
+    "uhc_env_live_begin", "uhc_env_live_push", "uhc_env_live_view", "uhc_env_live_end",
 ]
 
 
@@ -96,6 +97,12 @@ def lib():
     if hasattr(L, "uhc_smpl_qpos"):  # (additive within ABI 11)
         L.uhc_smpl_qpos.argtypes = [P, I, C.POINTER(I), P, I, P, P, C.c_int64, P, P, I, P, P]
         L.uhc_smpl_qpos.restype = I
+    if hasattr(L, "uhc_env_live_begin"):  # (additive within ABI 11)
+        L.uhc_env_live_begin.argtypes = [P, I, I, C.POINTER(I), C.POINTER(I), P, P, I, D, P]
+        L.uhc_env_live_push.argtypes = [P, P, I, P, P, P, P]
+        L.uhc_env_live_view.argtypes = [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I)]
+        L.uhc_env_live_end.argtypes = [P]
+        L.uhc_env_live_begin.restype = L.uhc_env_live_push.restype = L.uhc_env_live_view.restype = L.uhc_env_live_end.restype = I
     _lib = L
     return L
 

@@ -597,6 +597,40 @@ def _eval_seq(self, take_key, loader):
     return self.eval_seqs([take_key], loader)[take_key]
 
 
+@torch.no_grad()
+def _track_stream(self, source, n_steps, n_env=None, head=3):
+    """The agent's policy (mean action, frozen filter) follows a LIVE source instead of a clip of the bank: `source(t)` returns frame t of every env's
+    target motion as a device tensor (n_env, 76) -- hinge qpos rows, what smpl_qpos_device gives -- or None when there is no new frame.  Frames
+    0 .. head - 1 are asked for up front (head >= 2; with 3 the first step sees what it would see of a clip), frame t + head before step t
+    (uhc_amd.stream.StreamTracker on an env in live mode: VecHumanoidEnv.live_begin / live_push).  Returns (qpos (n_env, n_steps, nq), the step at
+    which each env's episode ended -- n_steps where it did not; the envs are stepped on after that), both on the device."""
+    from ..stream import StreamTracker
+    cfg = self.cfg
+    n = int(n_env or cfg.n_env)
+    if head < 2:
+        raise ValueError("track_stream: head must be at least 2 (a stream needs a pair of frames for its velocities)")
+    self._stream_envs = getattr(self, "_stream_envs", {})
+    ev = self._stream_envs.get(n)
+    if ev is None:
+        if self.env.use_quat:
+            raise NotImplementedError("track_stream: hinge qpos rows alone do not carry the ball-joint humanoid's record quaternion (StreamTracker takes root_quat_record)")
+        ev = self._stream_envs[n] = VecHumanoidEnv(cfg, n_env=n, device=self.env.device.index or 0, mode="test", model=self.env.body_model,
+                                                   shape_models=self.env.body_models[1:])
+    ev.set_rfc_rate(self.env.rfc_rate)
+    ev.live_begin(int(n_steps) + int(head) + 1)
+    tracker = StreamTracker(ev, self.policy_net, self.running_state, dtype=self.dtype)
+    tracker.begin(torch.stack([torch.as_tensor(source(t)).to(ev.device, torch.float64) for t in range(head)], 1))
+    out = torch.zeros((n, int(n_steps), int(ev.model.nq)), dtype=torch.float64, device=ev.device)
+    ended = torch.full((n,), int(n_steps), dtype=torch.int64, device=ev.device)
+    for t in range(int(n_steps)):
+        qpos, done = tracker.step(source(t + head))
+        out[:, t] = qpos
+        ended = torch.where((done != 0) & (ended == n_steps), torch.full_like(ended, t), ended)
+    ev.live_end()
+    return out, ended
+
+
+AgentCopycat.track_stream = _track_stream
 AgentCopycat.eval_policy = _eval_policy
 AgentCopycat.eval_seqs = _eval_seqs
 AgentCopycat.eval_seq = _eval_seq

@@ -7,7 +7,11 @@
 
 #include "../../include/uhc_amd.h"
 #include "uhc_device_env.h"
+#include "uhc_expert_math.h"  // XfTree: the kinematic tree uhc_env_live_push hands its kernel
 
+extern "C" hipError_t uhc_launch_live_push(const EnvArgs* E, const XfTree* tree, double dt, int cap, int n_models, double* bank, double* prev_qpos,
+                                           int* live_len, int* dropped, const double* body_pos, const double* body_ipos, const int* env_ids, int n,
+                                           const double* qpos, const double* root_record, const int* restart, const int* model, hipStream_t s);
 extern "C" hipError_t uhc_launch_env_pre(const EnvArgs* E, const int* d_active, hipStream_t s);
 extern "C" hipError_t uhc_launch_env_post(int mode, const EnvArgs* E, const double* d_action, const int* d_active, hipStream_t s);
 extern "C" hipError_t uhc_launch_env_reset_stage(const EnvArgs* E, const int* env_ids, int n, const double* noise, double* out_qpos,
@@ -39,7 +43,16 @@ struct UhcEnv {
     int* select = nullptr;
     int n_clips = 0;
     int64_t n_frames = 0;
+    // live targets (uhc_env_live_*): the env's own bank, one stream of `live_cap` frames per env; the memory stays until uhc_env_free
+    bool live = false;
+    int live_cap = 0, live_alloc_cap = 0, live_models = 0;
+    double live_dt = 0.0;
+    XfTree live_tree = {};
+    double *live_bank = nullptr, *live_prev_qpos = nullptr, *live_beta = nullptr, *live_body_pos = nullptr, *live_body_ipos = nullptr;
+    int *live_len = nullptr, *live_dropped = nullptr, *live_clip_start = nullptr;
 };
+#define NOT_WHILE_LIVE(e, who) \
+    if ((e)->live) return uhc_internal_set_error(who ": the env is in live mode (uhc_env_live_begin): a stream has no window to assign or queue -- push a restart row and uhc_env_reset, or uhc_env_live_end first")
 
 template <class T>
 static int dalloc(UhcEnv* e, size_t n, T** p) {
@@ -156,6 +169,7 @@ extern "C" int32_t uhc_env_field(UhcEnv* e, int32_t f, void** p, int64_t* n) {
 extern "C" int32_t uhc_env_set_bank(UhcEnv* e, const double* d_frames, int64_t n_frames, const int32_t* d_clip_start,
                                     const double* d_clip_beta, int32_t n_clips) {
     if (!e || !d_frames || !d_clip_start || !d_clip_beta || n_frames < 1 || n_clips < 1) return uhc_internal_set_error("uhc_env_set_bank: bad argument");
+    e->live = false;  // (a caller's bank ends live mode, like uhc_env_live_end)
     e->E.bank = d_frames; e->E.clip_start = d_clip_start; e->E.clip_beta = d_clip_beta;
     e->n_clips = n_clips; e->n_frames = n_frames;
     e->E.obj_pose = nullptr;  // rows of another bank
@@ -163,6 +177,7 @@ extern "C" int32_t uhc_env_set_bank(UhcEnv* e, const double* d_frames, int64_t n
 }
 extern "C" int32_t uhc_env_set_obj_pose(UhcEnv* e, const double* d_obj_pose, int64_t n_frames) {
     if (!e) return uhc_internal_set_error("uhc_env_set_obj_pose: null env");
+    NOT_WHILE_LIVE(e, "uhc_env_set_obj_pose");
     if (e->E.n_obj == 0) return d_obj_pose ? uhc_internal_set_error("uhc_env_set_obj_pose: the env was created with num_obj = 0") : 0;
     if (!d_obj_pose || !e->E.bank || n_frames != e->n_frames) return uhc_internal_set_error("uhc_env_set_obj_pose: one row of 7 num_obj numbers per frame of the clip bank (set the bank first)");
     e->E.obj_pose = d_obj_pose;
@@ -170,6 +185,7 @@ extern "C" int32_t uhc_env_set_obj_pose(UhcEnv* e, const double* d_obj_pose, int
 }
 extern "C" int32_t uhc_env_set_clip_models(UhcEnv* e, const int32_t* d_clip_model) {
     if (!e) return uhc_internal_set_error("uhc_env_set_clip_models: null env");
+    NOT_WHILE_LIVE(e, "uhc_env_set_clip_models");
     int n_models = 1;
     int* em = uhc_internal_env_model(e->b, &n_models);
     if (d_clip_model && (!em || n_models < 2)) return uhc_internal_set_error("uhc_env_set_clip_models: the batch was created with a single model");
@@ -184,6 +200,7 @@ static hipStream_t stream_of(UhcEnv* e) {
 }
 extern "C" int32_t uhc_env_assign(UhcEnv* e, const int32_t* ids, int32_t n, const int32_t* clip_ids, const int32_t* fr_start, const int32_t* fr_len) {
     if (!e || !ids || !clip_ids || !fr_start || !fr_len || n < 1) return uhc_internal_set_error("uhc_env_assign: bad argument");
+    NOT_WHILE_LIVE(e, "uhc_env_assign");
     if (!e->E.bank) return uhc_internal_set_error("uhc_env_assign: no clip bank set");
     HIP_OK(uhc_launch_env_assign(&e->E, ids, n, clip_ids, fr_start, fr_len, stream_of(e)));
     return 0;
@@ -203,6 +220,7 @@ extern "C" int32_t uhc_env_reset(UhcEnv* e, const int32_t* ids, int32_t n, const
 extern "C" int32_t uhc_env_set_next(UhcEnv* e, const int32_t* ids, int32_t n, const int32_t* clip_ids, const int32_t* fr_start, const int32_t* fr_len,
                                     const double* d_noise) {
     if (!e || !ids || !clip_ids || !fr_start || !fr_len || n < 1 || n > e->E.n_env) return uhc_internal_set_error("uhc_env_set_next: bad argument");
+    NOT_WHILE_LIVE(e, "uhc_env_set_next");
     if (!e->E.bank) return uhc_internal_set_error("uhc_env_set_next: no clip bank set");
     HIP_OK(uhc_launch_env_set_next(&e->E, ids, n, clip_ids, fr_start, fr_len, d_noise, stream_of(e)));
     return 0;
@@ -214,6 +232,7 @@ extern "C" int32_t uhc_env_set_end_reward(UhcEnv* e, double end_reward) {
 }
 extern "C" int32_t uhc_env_auto_reset(UhcEnv* e) {
     if (!e) return uhc_internal_set_error("uhc_env_auto_reset: null env");
+    NOT_WHILE_LIVE(e, "uhc_env_auto_reset");
     if (!e->E.bank) return uhc_internal_set_error("uhc_env_auto_reset: no clip bank set");
     if (e->E.n_obj > 0 && !e->E.obj_pose) return uhc_internal_set_error("uhc_env_auto_reset: the model has objects but no obj_pose rows are set (uhc_env_set_obj_pose)");
     hipStream_t s = stream_of(e);
@@ -229,5 +248,104 @@ extern "C" int32_t uhc_env_step(UhcEnv* e, const double* d_action, const int32_t
     HIP_OK(uhc_launch_env_pre(&e->E, d_active, s));
     if (uhc_batch_simulate(e->b, d_action, e->E.target_base, d_active)) return 1;
     HIP_OK(uhc_launch_env_post(0, &e->E, d_action, d_active, s));
+    return 0;
+}
+
+// ------------------------------------------------------------------ live targets (include/uhc_amd.h, "live targets"); the kernel is uhc_live.hip's
+static void* take_alloc(UhcEnv* e, void* p) {  // p leaves the env's allocation list (to be freed by the caller)
+    for (size_t i = 0; i < e->allocs.size(); i++)
+        if (e->allocs[i] == p) { e->allocs.erase(e->allocs.begin() + i); break; }
+    return p;
+}
+extern "C" int32_t uhc_env_live_begin(UhcEnv* e, int32_t cap, int32_t n_body, const int32_t* h_parent, const int32_t* h_ee_body, const double* d_body_pos,
+                                      const double* d_body_ipos, int32_t n_models, double dt, const double* d_beta) {
+    // the checks that do not read the env come first; e == NULL is the last one before any HIP call
+    if (cap < 2) return uhc_internal_set_error("uhc_env_live_begin: cap must be at least 2 (a stream needs a pair of frames for its velocities)");
+    if (n_body != XF_NBODY) return uhc_internal_set_error("uhc_env_live_begin: n_body must be 24 (UHC_FRAME_STRIDE is a 24-body layout)");
+    if (!h_parent) return uhc_internal_set_error("uhc_env_live_begin: h_parent is NULL");
+    if (!h_ee_body) return uhc_internal_set_error("uhc_env_live_begin: h_ee_body is NULL");
+    if (!d_body_pos) return uhc_internal_set_error("uhc_env_live_begin: d_body_pos is NULL");
+    if (!d_body_ipos) return uhc_internal_set_error("uhc_env_live_begin: d_body_ipos is NULL");
+    if (n_models <= 0) return uhc_internal_set_error("uhc_env_live_begin: n_models <= 0");
+    if (!(dt > 0.0)) return uhc_internal_set_error("uhc_env_live_begin: dt <= 0");
+    XfTree tree;
+    const std::string bad = xf_tree_fill("uhc_env_live_begin", h_parent, h_ee_body, &tree);
+    if (!bad.empty()) return uhc_internal_set_error(bad.c_str());
+    if (!e) return uhc_internal_set_error("uhc_env_live_begin: the env e is NULL");
+    int batch_models = 1;
+    int* em = uhc_internal_env_model(e->b, &batch_models);
+    if (n_models != batch_models)
+        return uhc_internal_set_error(("uhc_env_live_begin: n_models = " + std::to_string(n_models) + ", the batch was created with " + std::to_string(batch_models)).c_str());
+    if (e->E.n_obj > 0) return uhc_internal_set_error("uhc_env_live_begin: the env was created with num_obj > 0 (object poses per live frame are not supported)");
+    const size_t N = e->E.n_env;
+    if ((long long)N * cap > 0x7fffffffLL) return uhc_internal_set_error("uhc_env_live_begin: n_env x cap is beyond 2^31 - 1 frames");
+    HIP_OK(hipStreamSynchronize(stream_of(e)));  // (a step in flight may still read the bank the tables below are about to clear)
+    if (cap > e->live_alloc_cap) {
+        if (e->live) (void)uhc_env_live_end(e);  // (the bank about to be freed may be the installed one: no bank until this call succeeds)
+        if (e->live_bank) (void)hipFree(take_alloc(e, e->live_bank));
+        e->live_bank = nullptr, e->live_alloc_cap = 0;
+        void* q = nullptr;
+        if (hipMalloc(&q, N * cap * UHC_FRAME_STRIDE * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return uhc_internal_set_error(("uhc_env_live_begin: cap = " + std::to_string(cap) + ": no memory for n_env x cap x 4672 bytes").c_str());
+        }
+        e->allocs.push_back(q);
+        e->live_bank = (double*)q, e->live_alloc_cap = cap;
+    }
+    if (!e->live_len && (dalloc(e, N * XF_NQ, &e->live_prev_qpos) || dalloc(e, N, &e->live_len) || dalloc(e, N, &e->live_dropped) ||
+                         dalloc(e, N, &e->live_clip_start) || dalloc(e, N * 17, &e->live_beta) ||
+                         dalloc(e, (size_t)n_models * XF_NBODY * 3, &e->live_body_pos) || dalloc(e, (size_t)n_models * XF_NBODY * 3, &e->live_body_ipos)))
+        return 1;
+    hipStream_t s = stream_of(e);
+    HIP_OK(hipMemsetAsync(e->live_len, 0, N * sizeof(int), s));  // every stream is cleared: an append without a restart is dropped
+    HIP_OK(hipMemsetAsync(e->live_dropped, 0, N * sizeof(int), s));
+    HIP_OK(hipMemsetAsync(e->live_prev_qpos, 0, N * XF_NQ * sizeof(double), s));
+    // every slot is zeroed and every env points at a window of ONE frame inside its own stream: a reset or a step before the first push reads zeros,
+    // never a frame outside the bank (the env kernels clamp to e_len - 1, and e_start of an earlier bank means nothing here)
+    HIP_OK(hipMemsetAsync(e->live_bank, 0, N * cap * UHC_FRAME_STRIDE * sizeof(double), s));
+    std::vector<int> cs(N), ones(N, 1), iota(N);
+    for (size_t i = 0; i < N; i++) cs[i] = (int)(i * cap), iota[i] = (int)i;
+    HIP_OK(hipMemcpy(e->live_clip_start, cs.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(e->E.e_start, cs.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(e->E.e_len, ones.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(e->E.clip_id, iota.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    if (d_beta) HIP_OK(hipMemcpy(e->live_beta, d_beta, N * 17 * sizeof(double), hipMemcpyDeviceToDevice));
+    else HIP_OK(hipMemset(e->live_beta, 0, N * 17 * sizeof(double)));
+    HIP_OK(hipMemcpy(e->live_body_pos, d_body_pos, (size_t)n_models * XF_NBODY * 3 * sizeof(double), hipMemcpyDeviceToDevice));
+    HIP_OK(hipMemcpy(e->live_body_ipos, d_body_ipos, (size_t)n_models * XF_NBODY * 3 * sizeof(double), hipMemcpyDeviceToDevice));
+    HIP_OK(hipStreamSynchronize(s));
+    e->live = true, e->live_cap = cap, e->live_models = n_models, e->live_dt = dt, e->live_tree = tree;
+    e->E.bank = e->live_bank, e->E.clip_start = e->live_clip_start, e->E.clip_beta = e->live_beta;
+    e->E.obj_pose = nullptr, e->E.clip_model = nullptr, e->E.env_model = em;
+    e->n_clips = (int)N, e->n_frames = (int64_t)N * cap;
+    return 0;
+}
+extern "C" int32_t uhc_env_live_push(UhcEnv* e, const int32_t* d_env_ids, int32_t n, const double* d_qpos, const double* d_root_quat_record,
+                                     const int32_t* d_restart, const int32_t* d_model) {
+    if (!d_env_ids) return uhc_internal_set_error("uhc_env_live_push: d_env_ids is NULL");
+    if (!d_qpos) return uhc_internal_set_error("uhc_env_live_push: d_qpos is NULL");
+    if (n < 0) return uhc_internal_set_error("uhc_env_live_push: n < 0");
+    if (n == 0) return 0;  // (nothing to push: no launch, and nothing of the env is read)
+    if (!e) return uhc_internal_set_error("uhc_env_live_push: the env e is NULL");
+    if (!e->live) return uhc_internal_set_error("uhc_env_live_push: the env is not in live mode (uhc_env_live_begin)");
+    HIP_OK(uhc_launch_live_push(&e->E, &e->live_tree, e->live_dt, e->live_cap, e->live_models, e->live_bank, e->live_prev_qpos, e->live_len, e->live_dropped,
+                                e->live_body_pos, e->live_body_ipos, d_env_ids, n, d_qpos, d_root_quat_record, d_restart, d_model, stream_of(e)));
+    return 0;
+}
+extern "C" int32_t uhc_env_live_view(UhcEnv* e, double** d_frames, int32_t** d_len, int32_t** d_dropped, int32_t* cap) {
+    if (!e) return uhc_internal_set_error("uhc_env_live_view: the env e is NULL");
+    if (!e->live) return uhc_internal_set_error("uhc_env_live_view: the env is not in live mode (uhc_env_live_begin)");
+    if (d_frames) *d_frames = e->live_bank;
+    if (d_len) *d_len = e->live_len;
+    if (d_dropped) *d_dropped = e->live_dropped;
+    if (cap) *cap = e->live_cap;
+    return 0;
+}
+extern "C" int32_t uhc_env_live_end(UhcEnv* e) {
+    if (!e) return uhc_internal_set_error("uhc_env_live_end: the env e is NULL");
+    if (!e->live) return uhc_internal_set_error("uhc_env_live_end: the env is not in live mode (uhc_env_live_begin)");
+    e->live = false;
+    e->E.bank = nullptr, e->E.clip_start = nullptr, e->E.clip_beta = nullptr, e->E.clip_model = nullptr;
+    e->n_clips = 0, e->n_frames = 0;
     return 0;
 }

@@ -1,0 +1,117 @@
+// Live targets: one expert frame record per env and control step, appended to the env's own stream: uhc_env_live_push (include/uhc_amd.h).
+//
+// The per-env, per-step form of uhc_expert.hip: the same record (uhc_expert_math.h), from the pair (the env's previous row, the pushed row) instead of two
+// rows of a bank found by a binary search, written to slot `len` of the env's stream in the live bank [n_env][cap][UHC_FRAME_STRIDE], with the per-env
+// bookkeeping the env kernels read (e_len, e_start, clip_id, height_lb).  The entry points and the memory are uhc_env_capi.cpp's.
+//
+// Mapping: one wave per TWO rows (lanes 0 .. 31 the even one, lanes 32 .. 63 the odd one), four waves per workgroup; within a half, lane = body.  A half
+// whose row is ignored (env outside the batch) or dropped (no stream, or a full one) computes the wave's first row along and stores nothing: what the
+// halves do differs in data, not in control flow, and every wave reaches the barrier.  After the barrier the half copies its record out of LDS, 16 B per
+// lane to consecutive addresses (292 x 16 B), and -- when the row is the stream's frame 1 -- the 75 + 72 velocity slots into frame 0 as well (the
+// cat((qvel[0:1], qvel)) rule); its lanes then write the row to prev_qpos, and one lane the counters.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/uhc_amd.h"
+#include "uhc_device_env.h"
+#include "uhc_expert_math.h"
+
+#pragma clang fp contract(off)
+
+#define LV_WAVES 4  // waves per workgroup: eight rows
+
+struct LiveArgs {
+    // the call
+    const int* env_ids;         // [n]
+    const double* qpos;         // [n][76]
+    const double* root_record;  // [n][4] or NULL
+    const int* restart;         // [n] or NULL
+    const int* model;           // [n] or NULL
+    int n;
+    // the live state (owned by the UhcEnv)
+    double* bank;       // [n_env][cap][UHC_FRAME_STRIDE]
+    double* prev_qpos;  // [n_env][76]: the stream's newest row, with its OWN root quaternion
+    int* live_len;      // [n_env]
+    int* dropped;       // [n_env]
+    const double* body_pos;   // [n_models][24][3]
+    const double* body_ipos;  // [n_models][24][3]
+    int n_env, cap, n_models;
+    double dt;
+    XfTree tree;
+    // what the env kernels read (EnvArgs)
+    int *e_len, *e_start, *clip_id, *env_model;  // (env_model: NULL on a batch with one model)
+    double* height_lb;
+};
+
+__global__ void __launch_bounds__(64 * LV_WAVES) uhc_live_push_kernel(const LiveArgs A) {
+    __shared__ __attribute__((aligned(16))) double rec_s[2 * LV_WAVES][UHC_FRAME_STRIDE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, body = lane & 31;
+    const int r0 = (blockIdx.x * LV_WAVES + wave) * 2;  // the wave's rows: r0 (lanes 0 .. 31) and r0 + 1 (lanes 32 .. 63)
+    const bool wave_valid = r0 < A.n;                   // (wave-uniform; the barrier below is reached by every wave)
+    double* rec = rec_s[2 * wave + half];
+    // what the half does with its row (half-uniform): 0 nothing, 1 restart, 2 append, 3 drop
+    int what = 0, env = 0, L = 0, m = 0;
+    const double* row = A.qpos;
+    if (wave_valid) {
+        const int r = r0 + half < A.n ? r0 + half : r0;  // (the last row may have no partner)
+        row = A.qpos + (size_t)r * XF_NQ;
+        const int id = A.env_ids[r];
+        const bool ok = r0 + half < A.n && id >= 0 && id < A.n_env;  // (no read or write goes through an index outside the batch)
+        env = ok ? id : 0;
+        if (ok) {
+            L = A.live_len[env];
+            what = A.restart && A.restart[r] ? 1 : (L >= 1 && L < A.cap ? 2 : 3);
+            m = what == 1 && A.model ? A.model[r] : (A.env_model ? A.env_model[env] : 0);
+            m = m < 0 || m >= A.n_models ? 0 : m;
+        }
+        // the pair: (previous row, row) of an append; a restart is a clip of one frame, and so is what a half computes along
+        const bool append = what == 2;
+        const double* row_a = append ? A.prev_qpos + (size_t)env * XF_NQ : row;
+        const bool store = what == 1 || what == 2;
+        xf_half_record(A.tree, A.dt, row_a, row, !append, append, A.root_record && store ? A.root_record + (size_t)r * 4 : nullptr,
+                       A.body_pos + (size_t)m * XF_NBODY * 3, A.body_ipos + (size_t)m * XF_NBODY * 3, store, lane, rec);
+    }
+    __syncthreads();
+    if (what == 1 || what == 2) {
+        const int slot = what == 1 ? 0 : L;  // 0 <= slot < cap
+        double* stream0 = A.bank + (size_t)env * A.cap * UHC_FRAME_STRIDE;
+        // the half's record: one run of consecutive 16-byte stores (4 672 B per record: 16-byte aligned)
+        const double2* src = reinterpret_cast<const double2*>(rec);
+        double2* dst = reinterpret_cast<double2*>(stream0 + (size_t)slot * UHC_FRAME_STRIDE);
+        for (int j = body; j < UHC_FRAME_STRIDE / 2; j += 32) dst[j] = src[j];
+        if (what == 2 && L == 1) {  // frame 0 takes frame 1's velocities
+            for (int j = body; j < 75; j += 32) stream0[UHC_FR_QVEL + j] = rec[UHC_FR_QVEL + j];
+            for (int j = body; j < 72; j += 32) stream0[UHC_FR_BANGVEL + j] = rec[UHC_FR_BANGVEL + j];
+        }
+        for (int j = body; j < XF_NQ; j += 32) A.prev_qpos[(size_t)env * XF_NQ + j] = row[j];  // (every read of the previous row lies before the barrier)
+        if (body == 0) {
+            const double h = row[2];
+            A.live_len[env] = slot + 1;
+            A.e_len[env] = slot + 1;
+            if (what == 1) {
+                A.e_start[env] = env * A.cap;
+                A.clip_id[env] = env;
+                A.height_lb[env] = h;
+                A.dropped[env] = 0;
+                if (A.model && A.env_model) A.env_model[env] = m;
+            } else {
+                A.height_lb[env] = fmin(A.height_lb[env], h);
+            }
+        }
+    } else if (what == 3 && body == 0) {
+        A.dropped[env] += 1;
+    }
+}
+
+// E's per-env arrays and the live state -> one launch on s; n >= 1
+extern "C" hipError_t uhc_launch_live_push(const EnvArgs* E, const XfTree* tree, double dt, int cap, int n_models, double* bank, double* prev_qpos,
+                                           int* live_len, int* dropped, const double* body_pos, const double* body_ipos, const int* env_ids, int n,
+                                           const double* qpos, const double* root_record, const int* restart, const int* model, hipStream_t s) {
+    LiveArgs A = {};
+    A.env_ids = env_ids, A.qpos = qpos, A.root_record = root_record, A.restart = restart, A.model = model, A.n = n;
+    A.bank = bank, A.prev_qpos = prev_qpos, A.live_len = live_len, A.dropped = dropped, A.body_pos = body_pos, A.body_ipos = body_ipos;
+    A.n_env = E->n_env, A.cap = cap, A.n_models = n_models, A.dt = dt, A.tree = *tree;
+    A.e_len = E->e_len, A.e_start = E->e_start, A.clip_id = E->clip_id, A.env_model = E->env_model, A.height_lb = E->height_lb;
+    hipLaunchKernelGGL(uhc_live_push_kernel, dim3((unsigned)(((long long)n + 2 * LV_WAVES - 1) / (2 * LV_WAVES))), dim3(64 * LV_WAVES), 0, s, A);
+    return hipGetLastError();
+}

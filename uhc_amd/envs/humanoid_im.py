@@ -272,6 +272,48 @@ class VecHumanoidEnv:
         fl = torch.as_tensor(self._window_len(fr_start, fr_end), dtype=torch.int32)
         self.env.assign(torch.as_tensor(env_ids, dtype=torch.int32), cid, fs, fl)
 
+    # ---- live targets: the envs imitate frames that arrive while they run (a kinematic policy, a pose estimator, teleoperation) ----------
+    def live_begin(self, cap, beta=None):
+        """Every env gets a stream of up to `cap` frames in a bank the library owns (n_env x cap x 4 672 B) in place of the clip bank; beta
+        (n_env, 17) or None: what has_shape observations append.  Then: live_push(ids, rows, restart=ones) frame 0, live_push the frames that
+        are there, reset(ids), and one live_push per control step.  assign / set_next / auto_reset are refused until live_end / set_clip_bank."""
+        if self.num_obj:
+            raise NotImplementedError("live targets: object poses per live frame are not built")
+        for i, m in enumerate(self.body_models):
+            if i not in self._humanoids:
+                self._humanoids[i] = Humanoid(model=m)
+        self.env.live_begin(cap, [self._humanoids[i] for i in range(len(self.body_models))], beta=beta, dt=1 / 30)
+        self.clip_keys, self._clip_index, self._clip_len = [], {}, None
+
+    def live_push(self, env_ids, qpos, restart=None, root_quat_record=None, model=None):
+        """One hinge qpos row (76 wide: what smpl_to_qpose / smpl_qpos_device give) per listed env: appended to its stream, or frame 0 of a new one
+        where restart != 0 (on body shape `model`, when given).  The ball-joint humanoid passes the second conversion's root quaternion
+        (qpos_quat[:, 3:7]) as root_quat_record.  One launch; device tensors are taken as they are."""
+        if self.use_quat and root_quat_record is None:
+            raise ValueError("live_push: the ball-joint humanoid's record carries the root quaternion of the quaternion conversion: pass root_quat_record")
+        self.env.live_push(env_ids, qpos, restart=restart, root_quat_record=root_quat_record, model=model)
+
+    def live_push_smpl(self, env_ids, pose_aa, trans, restart=None, model=None):
+        """live_push from raw AMASS rows: pose_aa (n, 72), trans (n, 3) -> uhc_smpl_qpos -> uhc_env_live_push; no row visits the host.  model
+        (n,) host integers or None: whose root offset each row gets (and, at a restart, the env's body shape)."""
+        if self.cc_cfg.robot_cfg.get("model", "smpl") != "smpl":
+            raise NotImplementedError("only the options the copycat path uses are built (SURVEY.md 8f-4)")
+        n = int(torch.as_tensor(pose_aa).shape[0])
+        if n == 0:
+            return
+        cm = None if model is None else [int(m) for m in model]
+        with torch.cuda.device(self.device):
+            got = S.smpl_qpos_device(pose_aa, trans, np.arange(n), list(self.body_models), clip_model=cm, count_offset=self.cc_cfg.robot_cfg.get("mesh", True),
+                                     want=("qpos", "qpos_quat") if self.use_quat else ("qpos",), device=self.device)
+            self.env.live_push(env_ids, got[0], restart=restart, root_quat_record=got[1][:, 3:7] if self.use_quat else None,
+                               model=None if cm is None else torch.tensor(cm, dtype=torch.int32))
+
+    def live_view(self):
+        return self.env.live_view()
+
+    def live_end(self):
+        self.env.live_end()
+
     # ---- gym-like batched surface -----------------------------------------------------------------------
     def set_mode(self, mode):
         self.mode = mode

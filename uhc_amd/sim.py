@@ -392,6 +392,7 @@ class EnvBatch:
         check(self.L.uhc_env_set_bank(self._e, C.c_void_p(frames.data_ptr()), frames.shape[0], C.c_void_p(clip_start.data_ptr()),
                                       C.c_void_p(clip_beta.data_ptr()), clip_start.shape[0]))
         self._bank = (frames, clip_start, clip_beta)  # keep alive: the library borrows the pointers
+        self._live = None  # (a caller's bank ends live mode)
 
     def set_obj_pose(self, obj_pose: Optional[torch.Tensor]):
         """expert["obj_pose"] of every frame of the bank ([n_frames][7 num_obj]): where a reset puts the objects (humanoid_im.py:1284-1287)."""
@@ -477,6 +478,70 @@ class EnvBatch:
 
     def set_end_reward(self, v: float):
         check(self.L.uhc_env_set_end_reward(self._e, float(v)))
+
+    # ---- live targets (uhc_env_live_*): each env imitates a stream of frames appended while it runs
+    def live_begin(self, cap: int, humanoids, beta: Optional[torch.Tensor] = None, dt: float = 1 / 30):
+        """Give every env a stream of up to `cap` frames in a bank the LIBRARY owns (n_env x cap x 4 672 B) and make it the env's clip bank.
+          humanoids: one `Humanoid` (or a list, same tree) per model of the batch -- their offset tables are copied --; beta (n_env, 17) or None (zeros):
+          what has_shape observations append.  Every stream starts empty: `live_push(..., restart=1)` its frame 0, push on, then `reset`."""
+        hs = list(humanoids) if isinstance(humanoids, (list, tuple)) else [humanoids]
+        parents = np.ascontiguousarray(hs[0]._parents, dtype=np.int32)
+        ee = np.ascontiguousarray(hs[0]._ee_idx, dtype=np.int32)
+        for h in hs[1:]:
+            if not np.array_equal(np.asarray(h._parents), parents) or list(h._ee_idx) != list(ee):
+                raise ValueError("live_begin: every body shape must share the first one's tree")
+        if ee.shape != (5,):
+            raise ValueError("live_begin: five end effectors (SMPL_EE_NAMES) are what the frame record holds")
+        self.generation += 1
+        off = torch.stack([h._offsets for h in hs]).to(self.device, torch.float64).contiguous()
+        ioff = torch.stack([h._i_offsets for h in hs]).to(self.device, torch.float64).contiguous()
+        b = None
+        if beta is not None:
+            b = torch.as_tensor(beta).to(self.device, torch.float64).contiguous()
+            if tuple(b.shape) != (self.n_env, 17):
+                raise ValueError(f"live_begin: beta must be ({self.n_env}, 17), got {tuple(b.shape)}")
+        torch.cuda.current_stream(self.device).synchronize()  # (the tables above are copied by the call, on the library's side)
+        check(self.L.uhc_env_live_begin(self._e, int(cap), int(off.shape[1]), parents.ctypes.data_as(C.POINTER(C.c_int32)), ee.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        C.c_void_p(off.data_ptr()), C.c_void_p(ioff.data_ptr()), len(hs), float(dt), None if b is None else C.c_void_p(b.data_ptr())))
+        self._bank = None
+        self._live = None
+
+    def live_push(self, env_ids, qpos, restart=None, root_quat_record=None, model=None):
+        """One row (76 wide, as `expert_frames_device` takes them) per listed env, appended to its stream -- or, where restart != 0, frame 0 of a new
+        one (on `model`'s body shape, when given) --: ONE launch, no host read; device tensors of the right type are taken as they are, so the call can
+        be captured into a graph.  Each env at most once per call.  A row for an env without a stream, or with a full one, is counted in `dropped`."""
+        ids = self._i32(torch.as_tensor(env_ids), self.device)
+        q = torch.as_tensor(qpos).to(self.device, torch.float64).contiguous()
+        n = int(ids.shape[0])
+        if ids.ndim != 1 or tuple(q.shape) != (n, 76):
+            raise ValueError(f"live_push: env_ids (n,) and qpos (n, 76) expected, got {tuple(ids.shape)} and {tuple(q.shape)}")
+        rq = None if root_quat_record is None else torch.as_tensor(root_quat_record).to(self.device, torch.float64).contiguous()
+        if rq is not None and tuple(rq.shape) != (n, 4):
+            raise ValueError(f"live_push: root_quat_record must be ({n}, 4), got {tuple(rq.shape)}")
+        rs = None if restart is None else self._i32(torch.as_tensor(restart), self.device)
+        md = None if model is None else self._i32(torch.as_tensor(model), self.device)
+        for name, t in (("restart", rs), ("model", md)):
+            if t is not None and tuple(t.shape) != (n,):
+                raise ValueError(f"live_push: {name} must be ({n},), got {tuple(t.shape)}")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        check(self.L.uhc_env_live_push(self._e, ptr(ids), n, ptr(q), ptr(rq), ptr(rs), ptr(md)))
+        self._keep_live = (ids, q, rq, rs, md)  # alive until the stream has consumed them (the next call replaces them a step later)
+
+    def live_view(self):
+        """(frames (n_env, cap, FRAME_STRIDE), len (n_env,), dropped (n_env,)): zero-copy torch views of the live bank and its counters."""
+        if getattr(self, "_live", None) is None:
+            pf, pl, pd, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+            check(self.L.uhc_env_live_view(self._e, C.byref(pf), C.byref(pl), C.byref(pd), C.byref(cap)))
+            self._live = (torch.as_tensor(_DevView(pf.value, (self.n_env, cap.value, FRAME_STRIDE), "<f8", self), device=self.device),
+                          torch.as_tensor(_DevView(pl.value, (self.n_env,), "<i4", self), device=self.device),
+                          torch.as_tensor(_DevView(pd.value, (self.n_env,), "<i4", self), device=self.device))
+        return self._live
+
+    def live_end(self):
+        """Leave live mode: the env has no bank until the next `set_bank` / `live_begin` (the live memory stays the env's)."""
+        self.generation += 1
+        check(self.L.uhc_env_live_end(self._e))
+        self._live = None
 
     def step(self, action: torch.Tensor, active: Optional[torch.Tensor] = None):
         assert action.dtype == torch.float64 and action.is_contiguous() and action.shape == (self.n_env, self.sim.ctrl.action_dim)

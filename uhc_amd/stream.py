@@ -1,0 +1,46 @@
+"""Tracking a live source: a frozen imitation policy follows target poses that arrive one per control step (a kinematic policy as in the
+reference's uhc/envs/humanoid_kin_v1.py, a pose estimator, a motion generator, teleoperation).  The targets go into the envs' streams with
+`VecHumanoidEnv.live_push` (uhc_env_live_push: one launch, no host FK, no upload of frame records, no new clip bank); the policy and the filter are the
+caller's.  Nothing here reads the device back: `step` returns views."""
+from __future__ import annotations
+
+import torch
+
+from . import sim as S
+
+
+class StreamTracker:
+    """env: a `VecHumanoidEnv` in live mode (`env.live_begin(cap)`); policy_net: a policy with `select_action(state, mean_action)`; running_state: the
+    policy's observation filter (ZFilter) or None -- applied with update=False, the statistics are those the policy was trained with."""
+
+    def __init__(self, env, policy_net, running_state=None, dtype=torch.float64):
+        self.env, self.policy_net, self.running_state, self.dtype = env, policy_net, running_state, dtype
+        self._ids = torch.arange(env.n_env, dtype=torch.int32, device=env.device)
+        self._ones = torch.ones(env.n_env, dtype=torch.int32, device=env.device)
+
+    def _state(self):
+        obs = self.env.obs.to(self.dtype)
+        return self.running_state(obs, update=False) if self.running_state is not None else obs
+
+    def begin(self, head, root_quat_record=None):
+        """head (n_env, k >= 2, 76): the first k target rows of every env's stream (device or host).  Frame 0 restarts the streams, the others are
+        appended, the envs are reset onto frame 0; returns the observation view.  root_quat_record (n_env, k, 4): the ball-joint humanoid's."""
+        head = torch.as_tensor(head).to(self.env.device, torch.float64)
+        if head.ndim != 3 or head.shape[0] != self.env.n_env or head.shape[1] < 2 or head.shape[2] != 76:
+            raise ValueError(f"StreamTracker.begin: head must be ({self.env.n_env}, k >= 2, 76), got {tuple(head.shape)}")
+        for t in range(head.shape[1]):
+            self.env.live_push(self._ids, head[:, t].contiguous(), restart=self._ones if t == 0 else None,
+                               root_quat_record=None if root_quat_record is None else torch.as_tensor(root_quat_record)[:, t])
+        self.env.reset(self._ids)
+        return self.env.obs
+
+    def step(self, next_qpos=None, restart=None, root_quat_record=None):
+        """One control step of every env: mean action of the policy on the filtered observation; `next_qpos` (n_env, 76), when given, is appended to the
+        streams BEFORE the step (restart (n_env,): non-zero rows start a new stream instead -- the caller resets those envs).  Returns (qpos view
+        (n_env, nq), done view (n_env,))."""
+        with torch.no_grad():
+            action = self.policy_net.select_action(self._state(), True).to(torch.float64).contiguous()
+        if next_qpos is not None:
+            self.env.live_push(self._ids, next_qpos, restart=restart, root_quat_record=root_quat_record)
+        self.env.step(action)
+        return self.env.sim.field(S.F_QPOS), self.env.done
