@@ -71,7 +71,7 @@ class Exec:
         return False
 
 
-SAVE = re.compile(r"^s_(and|andn2|andn1|or|xor|nand|nor|xnor)_saveexec_b64\s+(s\[\d+:\d+\]|vcc)")
+SAVE = re.compile(r"^s_(and|andn2|andn1|or|xor|nand|nor|xnor)_saveexec_b64\s+(s\[\d+:\d+\]|vcc)(?:,\s*(\S+))?")
 NARROW = re.compile(r"^s_(and|andn2)_b64\s+exec,\s*exec,")
 RESTORE = re.compile(r"^s_(or|mov|xor)_b64\s+exec,\s*(?:exec,\s*)?(s\[\d+:\d+\]|vcc|-1)")
 COPY = re.compile(r"^s_mov_b64\s+(s\[\d+:\d+\]|vcc),\s*exec")
@@ -100,7 +100,12 @@ def lint_kernel(name, lines):
         m = SAVE.search(ins)
         if m:
             saved[m.group(2)] = cur
-            cur = Exec(cur) if m.group(1) in ("and", "andn2", "andn1") else Exec(None)  # (or / xor / ... saveexec: not a subset of the old mask: an unrelated state)
+            if m.group(1) == "or" and m.group(3) == "-1":
+                # EXEC | -1: every lane on, as after s_mov_b64 exec, -1 -- how the compiler reloads a VGPR that holds spilled SGPRs in its lanes (v_writelane /
+                # v_readlane) when that VGPR was itself spilled to scratch: all lanes are loaded, then EXEC is put back
+                cur = root
+            else:
+                cur = Exec(cur) if m.group(1) in ("and", "andn2", "andn1") else Exec(None)  # (or / xor / ... saveexec: not a subset of the old mask: an unrelated state)
             stats["regions"] += 1
             continue
         m = COPY.search(ins)

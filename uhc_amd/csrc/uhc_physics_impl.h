@@ -2847,7 +2847,11 @@ __device__ __forceinline__ int uhc_step_env(const KernelArgs& A, const double* _
     for (int i = LANE; i < L.total; i += UHC_WAVE) S[i] = __longlong_as_double(UHC_POISON_BITS);
     wsync();
 #endif
-    const double* mb = A.s.model_blob + (size_t)(A.s.env_model ? A.s.env_model[env] : 0) * A.o.stride;
+    // (`env` is wave-uniform, but the word comes back from a vector load: without the readfirstlane `mb` is a 64-bit VGPR pair and so is every address
+    //  formed from it -- some fifty of them, loop invariants of the substep loop that were spilled ahead of it and reloaded stage by stage; as a scalar
+    //  base the blob's tables are addressed SGPR pair + 32-bit lane offset)
+    const int env_model = A.s.env_model ? __builtin_amdgcn_readfirstlane(A.s.env_model[env]) : 0;
+    const double* mb = A.s.model_blob + (size_t)env_model * A.o.stride;
     // tier trace (UHC_DEBUG_TRACE, product builds; tools/tier_trace.py): when each tier took the env up and let it go (100 MHz wall clock)
     // and the substep of a hand-on, in the first words of the env's stage-profile record
 #ifndef UHC_STAGE_PROF
