@@ -29,7 +29,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define UHC_ABI_VERSION 11  /* 11: uhc_expert_frames (the clip bank's frame records computed on the device) -- uhc_eval_record / uhc_eval_metrics came later and are purely additive: still 11; 10: uhc_build_flags; 9: UHC_F_REDO bits 29 / 30 (tier 4), swept-substep bits 8 .. 28; uhc_rollout_record counts int64 [7] */
+#define UHC_ABI_VERSION 11  /* 11: uhc_expert_frames (the clip bank's frame records computed on the device) -- uhc_eval_record / uhc_eval_metrics came later and are purely additive: still 11, as are uhc_surface_* / uhc_eval_record_pose; 10: uhc_build_flags; 9: UHC_F_REDO bits 29 / 30 (tier 4), swept-substep bits 8 .. 28; uhc_rollout_record counts int64 [7] */
 
 /* joint / geom type codes (MuJoCo numbering) */
 enum { UHC_JNT_FREE = 0, UHC_JNT_BALL = 1, UHC_JNT_SLIDE = 2, UHC_JNT_HINGE = 3 };
@@ -561,6 +561,47 @@ int32_t uhc_eval_record(void* stream, int32_t phase, int32_t n_env, int32_t n_bo
 int32_t uhc_eval_metrics(void* stream, int32_t n_env, int32_t n_body, int32_t nqh, int32_t row_cap, const int32_t* d_rows, const double* d_pred_qpos,
                          const double* d_pred_jpos, const int64_t* d_gt_frame, const double* d_frames, int64_t n_frames, double* d_row_metrics,
                          double* d_clip_means, int32_t* d_bad, int32_t* h_bad);
+
+/* ------------------------------------------------------------------ contact quality of a motion: penetration, skate, float, contact count
+ * compute_penetration / compute_skate (uhc/smpllib/smpl_eval.py:125-149) on the device.  The reference scores SMPL surface vertices; this library scores the
+ * convex-hull vertices every compiled model carries in the body frame (mesh hulls; sphere and capsule cores with their radius) -- a DEVIATION -- and adds
+ * `float`, which the reference does not have.  Same conventions as the evaluation functions above: `stream` is a hipStream_t (NULL = the default stream),
+ * every argument is checked before the first HIP call, reductions have a fixed order and no floating-point atomics (two runs are bit-identical), no index or
+ * counter, whatever it holds, sends a read or a write outside the arrays.  (Purely additive: UHC_ABI_VERSION stays 11.)
+ *
+ * World vertex w = xpos[b] + R(xquat[b]) v for a vertex v of body b; height h = w.z - radius - floor_z; float64, products and sums rounded separately.
+ * Per row r of a sequence of T rows, in mm:
+ *   pen[r]      -mean(h over the vertices with h < 0) * 1000; 0 when there is none
+ *   skate[r]    r <= T - 2: mean of |w_xy[r + 1] - w_xy[r]| * 1000 over the vertices with h <= 0 in both rows; 0 when there is none
+ *   float[r]    min(h) * 1000 when every vertex has h > 0, else 0
+ *   contact[r]  the number of vertices with h <= 0, as a double
+ * A row whose n_body poses hold a non-finite number gets NaN in its four values and in the skate of the row before it, and counts 1 in d_bad.
+ *
+ * uhc_surface_create copies the host tables to the device (the current one): h_vert_body int32 [n_vert] (0 .. n_body - 1), h_vert_radius [n_vert] or NULL
+ *   (all zero), h_vert [n_models][n_vert][3]: the same topology on n_models body shapes.  Refused: n_body outside 1 .. 64, n_vert outside 1 .. 65535,
+ *   n_models < 1, a body outside the range, a negative or non-finite radius, a non-finite vertex.
+ * uhc_surface_metrics scores n_seq sequences.  Row i of sequence s is global row d_seq_start[s] + i (i < d_seq_rows[s], clamped to 0 .. row_cap); its
+ *   positions lie at d_pos + global_row * pos_stride as [n_body][3], its quaternions (w, x, y, z) at d_quat + global_row * quat_stride as [n_body][4]; the
+ *   strides are in doubles.  So one entry point reads a pose record (uhc_eval_record_pose: stride 168, offsets 0 and 72) and the clip bank (stride
+ *   UHC_FRAME_STRIDE, base pointers at the frames' world body positions and quaternions, offsets 151 and 223).
+ *   d_seq_model int32 [n_seq] or NULL: the body shape of each sequence; an entry outside 0 .. n_models - 1 reads as 0.
+ *   d_row_out [n_rows_total][4]: pen, skate, float, contact of every global row of a sequence (skate: not of its last row); other slots are left untouched.
+ *   d_seq_means [n_seq][4]: the means over T, T - 1, T, T rows in row order; over no row: NaN.
+ *   d_bad int32 [1]: set by the call to the number of rows with a non-finite pose plus the number of sequences whose rows would leave 0 .. n_rows_total
+ *                  (such a sequence is skipped: nothing of it is read or written).
+ *   h_bad (HOST, may be NULL): when given, the call waits for the stream and stores d_bad's count there.  n_seq == 0 succeeds and launches nothing.
+ * uhc_eval_record_pose appends xpos[1 .. 24] and xquat[1 .. 24] of every env uhc_eval_record's rule selects (d_alive[e] != 0, and phase == 0 or d_done[e], and
+ *   0 <= d_rows[e] < row_cap) to row d_rows[e] of d_pose [n_env][row_cap][168] (72 position doubles, then 96 quaternion doubles).  It reads d_rows and does
+ *   not write it: enqueue it on the same stream directly BEFORE uhc_eval_record of the same snapshot, which advances the counter.  d_done may be NULL in phase 0. */
+typedef struct UhcSurface UhcSurface;
+int32_t uhc_surface_create(int32_t n_body, int32_t n_vert, int32_t n_models, const int32_t* h_vert_body, const double* h_vert_radius, const double* h_vert,
+                           UhcSurface** out);
+void uhc_surface_free(UhcSurface* s);
+int32_t uhc_surface_metrics(void* stream, const UhcSurface* surf, int32_t n_seq, const int64_t* d_seq_start, const int32_t* d_seq_rows, int32_t row_cap,
+                            const int32_t* d_seq_model, const double* d_pos, int64_t pos_stride, const double* d_quat, int64_t quat_stride,
+                            int64_t n_rows_total, double floor_z, double* d_row_out, double* d_seq_means, int32_t* d_bad, int32_t* h_bad);
+int32_t uhc_eval_record_pose(void* stream, int32_t phase, int32_t n_env, int32_t nbody, int32_t row_cap, const double* d_xpos, const double* d_xquat,
+                             const int32_t* d_done, const int32_t* d_alive, const int32_t* d_rows, double* d_pose);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -481,6 +481,28 @@ def g11_metrics(dm, feat):
     save("g11_metrics", pred=pred, gt=gt, pred_jpos=pj, gt_jpos=gj, **{("m_" + k): np.asarray(v) for k, v in out.items()})
 
 
+def g17_surface():
+    """compute_penetration / compute_skate (uhc/smpllib/smpl_eval.py:125-149) on float64 vertex tensors: 20 frames of 200 hull-like vertices on 3 moving
+    bodies, some below, some on their way through the floor.  The poses and body-frame vertices travel with the world vertices, so that the device's
+    arithmetic (uhc_surface_math.h) can be run from the same inputs."""
+    from uhc.smpllib.smpl_eval import compute_penetration, compute_skate
+    from uhc_amd.smpllib.smpl_eval import hull_vertices
+    rng = np.random.default_rng(1717)
+    T, V, B = 20, 200, 3
+    vert = rng.uniform(-0.25, 0.25, size=(V, 3))
+    body = rng.integers(0, B, size=V).astype(np.int32)
+    quat = rng.normal(size=(T, B, 4)); quat /= np.linalg.norm(quat, axis=-1, keepdims=True)
+    pos = np.cumsum(rng.normal(scale=0.02, size=(T, B, 3)), axis=0)
+    pos[:, :, 2] += np.array([0.05, 0.3, -0.1])
+    world = hull_vertices((vert, body, np.zeros(V)), pos, quat)
+    assert np.abs(world[:, :, 2]).min() > 1e-6  # no comparison hangs on the last bit of a height
+    info = {"floor_z": 0}
+    pen = np.array(compute_penetration(torch.from_numpy(world), info))
+    skate = np.array(compute_skate(torch.from_numpy(world), info))
+    assert (pen > 0).any() and (skate > 0).any()
+    save("g17_surface", vert=vert, vert_body=body, pos=pos, quat=quat, pen=pen, skate=skate)  # (the world vertices are hull_vertices of these, to the bit)
+
+
 # --------------------------------------------------------------------------- G9 clip sampling
 def synth_pickle(rng):
     """8 small clips: mixed lengths (one below t_min+1), beta 10/16 wide, three genders."""
@@ -775,6 +797,7 @@ def main():
     g13_process_amass()
     g15_config_all()
     g16_boundary_helpers()
+    g17_surface()
 
 
 if __name__ == "__main__":

@@ -22,6 +22,7 @@ SYMBOLS = [
     "uhc_rollout_act", "uhc_rollout_record", "uhc_filter_scratch_doubles", "uhc_filter_push", "uhc_filter_apply",
     "uhc_expert_frames", "uhc_eval_record", "uhc_eval_metrics", "uhc_smpl_qpos",
     "uhc_env_live_begin", "uhc_env_live_push", "uhc_env_live_view", "uhc_env_live_end",
+    "uhc_surface_create", "uhc_surface_free", "uhc_surface_metrics", "uhc_eval_record_pose",
 ]
 
 
@@ -103,6 +104,13 @@ def lib():
         L.uhc_env_live_view.argtypes = [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I)]
         L.uhc_env_live_end.argtypes = [P]
         L.uhc_env_live_begin.restype = L.uhc_env_live_push.restype = L.uhc_env_live_view.restype = L.uhc_env_live_end.restype = I
+    if hasattr(L, "uhc_surface_create"):  # (additive within ABI 11)
+        L.uhc_surface_create.argtypes = [I, I, I, P, P, P, C.POINTER(P)]
+        L.uhc_surface_free.argtypes = [P]
+        L.uhc_surface_free.restype = None
+        L.uhc_surface_metrics.argtypes = [P, P, I, P, P, I, P, P, C.c_int64, P, C.c_int64, C.c_int64, D, P, P, P, C.POINTER(I)]
+        L.uhc_eval_record_pose.argtypes = [P, I, I, I, I, P, P, P, P, P, P]
+        L.uhc_surface_create.restype = L.uhc_surface_metrics.restype = L.uhc_eval_record_pose.restype = I
     _lib = L
     return L
 

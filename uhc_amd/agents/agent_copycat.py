@@ -416,6 +416,11 @@ def _eval_seqs(self, take_keys, loader):
     frames, starts = ev.env._bank[0], ev.env._bank[1].cpu().numpy()
     if getattr(cfg, "eval_build", "host") == "device":
         return _eval_seqs_device(self, ev, take_keys, loader, n)
+    surf = bool(getattr(cfg, "eval_surface", False))  # contact quality on the hull vertices: the loop also keeps xpos / xquat of bodies 1 .. body_lim - 1
+    if surf:
+        from ..smpllib.smpl_eval import hull_vertices, surface_tables
+        tables = [surface_tables(bm, ev.body_lim) for bm in ev.body_models]
+        clip_model = getattr(self, "_clip_model", None) or {}
     for c0 in range(0, len(take_keys), n):
         keys = take_keys[c0:c0 + n]
         m = len(keys)
@@ -430,6 +435,7 @@ def _eval_seqs(self, take_keys, loader):
         active = torch.zeros(n, dtype=torch.int32, device=ev.device)
         active[:m] = 1
         rec = {k: [[] for _ in range(m)] for k in ("gt", "pred", "gt_jpos", "pred_jpos", "reward")}
+        poses = [[] for _ in range(m)]  # (eval_surface) per row: 3 (body_lim - 1) positions, then 4 (body_lim - 1) quaternions
         fail_safe = np.zeros(m, dtype=bool)
         alive = np.ones(m, dtype=bool)
         clip0 = np.array([starts[ev._clip_index[k]] for k in keys])
@@ -445,6 +451,10 @@ def _eval_seqs(self, take_keys, loader):
             for e in np.nonzero(alive)[0]:
                 rec["pred"][e].append(q[e]); rec["pred_jpos"][e].append(x[e])
                 rec["gt"][e].append(g[e, 0:76]); rec["gt_jpos"][e].append(g[e, 151:223])
+            if surf:
+                xq = ev.sim.field(S.F_XQUAT)[:m].cpu().numpy()[:, 4:4 * bl]
+                for e in np.nonzero(alive)[0]:
+                    poses[e].append(np.concatenate([x[e], xq[e]]))
             return g
 
         percent = np.zeros(m)
@@ -463,9 +473,12 @@ def _eval_seqs(self, take_keys, loader):
                 gi = clip0 + np.minimum(t, lens - 1)
                 g = frames[torch.from_numpy(gi).to(frames.device)].cpu().numpy()
                 tele = []
+                xq = ev.sim.field(S.F_XQUAT)[:m].cpu().numpy()[:, 4:4 * bl] if surf else None
                 for e in np.nonzero(done)[0]:
                     rec["pred"][e].append(q[e]); rec["pred_jpos"][e].append(x[e])
                     rec["gt"][e].append(g[e, 0:76]); rec["gt_jpos"][e].append(g[e, 151:223])
+                    if surf:
+                        poses[e].append(np.concatenate([x[e], xq[e]]))
                     if cfg.fail_safe and pct[e] != 1:  # teleport to the expert state and keep going (humanoid_im.py:902-905)
                         fail_safe[e] = True
                         tele.append(e)
@@ -490,6 +503,9 @@ def _eval_seqs(self, take_keys, loader):
             res = {kk: np.vstack(v[e]) for kk, v in rec.items() if kk != "reward"}
             res["reward"] = np.array(rec["reward"][e])
             res["percent"], res["fail_safe"] = percent[e], bool(fail_safe[e])
+            if surf:  # compute_metrics scores the vertices and drops them again
+                pz = np.vstack(poses[e])
+                res["pred_vertices"] = hull_vertices(tables[int(clip_model.get(k, 0))], pz[:, :3 * (bl - 1)], pz[:, 3 * (bl - 1):])
             res.update(compute_metrics(res, None))
             out[k] = res
     return out
@@ -500,7 +516,8 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
     trajectory is appended on the device (uhc_eval_record) and scored there (uhc_eval_metrics).  The step loop reads nothing back when cfg.fail_safe is
     off -- it runs max(lens) steps, then looks at the number of envs still alive, and goes on in short blocks while there are any --; with cfg.fail_safe
     it reads the list of envs to teleport once per step.  One copy per chunk brings rows, rewards and metrics to the host, where the per-clip dicts of
-    the host path are cut from it."""
+    the host path are cut from it.  With cfg.eval_surface the body poses are appended beside every row (uhc_eval_record_pose, directly before each
+    uhc_eval_record), one uhc_surface_metrics launch scores them after the loop, and the clip means and the per-row contact counts ride in that copy."""
     from .. import eval_ops as EO
     from .. import sim as S
     cfg = self.cfg
@@ -509,6 +526,14 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
     frames, starts = ev.env._bank[0], ev.env._bank[1].cpu().numpy()
     ql = ev.qpos_lim
     nm = len(EO.METRICS)
+    surf = bool(getattr(cfg, "eval_surface", False))  # contact quality on the hull vertices: poses recorded beside the rows, one launch scores them
+    if surf:
+        self._eval_surfaces = getattr(self, "_eval_surfaces", {})
+        surface = self._eval_surfaces.get(id(ev))
+        if surface is None:
+            with torch.cuda.device(dev):
+                surface = self._eval_surfaces[id(ev)] = EO.Surface(list(ev.body_models), body_lim=ev.body_lim)
+        clip_model = getattr(self, "_clip_model", None) or {}
     for c0 in range(0, len(take_keys), n):
         keys = take_keys[c0:c0 + n]
         m = len(keys)
@@ -527,15 +552,20 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
         lens_d = torch.ones(n, dtype=torch.int32, device=dev)
         lens_d[:m] = torch.from_numpy(lens.astype(np.int32)).to(dev)
         block = int(lens.max())
-        rec = EO.Record(n, 2 * block + 2, ql, dev)
+        rec = EO.Record(n, 2 * block + 2, ql, dev, poses=surf)
         qpos_f, xpos_f, pct_f = ev.sim.field(S.F_QPOS), ev.sim.field(S.F_XPOS), ev.env.field(S.E_PERCENT)
+        xquat_f = ev.sim.field(S.F_XQUAT) if surf else None
         t = 0
 
         def step():
             nonlocal state
+            if surf:
+                EO.record_pose(rec, 0, xpos_f, xquat_f, active)
             EO.record(rec, 0, t, qpos_f, xpos_f, clip0, lens_d, active)
             action = self.policy_net.select_action(self.trans_policy(state), True).to(torch.float64).contiguous()
             ev.step(action, active)
+            if surf:
+                EO.record_pose(rec, 1, xpos_f, xquat_f, active, done=ev.done)
             EO.record(rec, 1, t, qpos_f, xpos_f, clip0, lens_d, active, done=ev.done, reward=ev.reward, percent=pct_f, fail_safe=cfg.fail_safe)
             if cfg.fail_safe:
                 ti = rec.tele.nonzero()[:, 0]  # (the one read of a fail-safe step: how many envs teleport)
@@ -557,22 +587,29 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
             block = 16
 
         row_metrics, _, bad = EO.metrics(rec, frames)
+        if surf:
+            seq_model = torch.zeros(n, dtype=torch.int32, device=dev)
+            seq_model[:m] = torch.tensor([int(clip_model.get(k, 0)) for k in keys], dtype=torch.int32).to(dev)
+            srow, smeans, sbad = EO.surface_metrics_of_record(surface, rec, seq_model=seq_model)
+            bad = bad + sbad  # (a non-finite pose: the same refusal below)
         # ---- one copy: [per-env words | overflow, bad | every valid row: pred, pred_jpos, gt, gt_jpos, metrics | every reward]
         ar = torch.arange(rec.row_cap, device=dev)[None]
         rmask, smask = ar < rec.rows[:, None], ar < rec.steps[:, None]
         gi = rec.gt_frame[rmask].clamp(0, frames.shape[0] - 1)
         g = frames[gi]
-        rows_d = torch.cat([rec.pred_qpos[rmask], rec.pred_jpos[rmask], g[:, 0:76], g[:, 151:223], row_metrics[rmask]], 1)
-        words = torch.stack([rec.rows.double(), rec.steps.double(), rec.fail_safe.double(), rec.percent], 1)
+        rows_d = torch.cat([rec.pred_qpos[rmask], rec.pred_jpos[rmask], g[:, 0:76], g[:, 151:223], row_metrics[rmask]] + ([srow[rmask][:, 3:4]] if surf else []), 1)
+        words = torch.stack([rec.rows.double(), rec.steps.double(), rec.fail_safe.double(), rec.percent] + ([smeans[:, i] for i in range(3)] if surf else []), 1)
         flat = torch.cat([words.reshape(-1), rec.overflow.double(), bad.double(), rows_d.reshape(-1), rec.rewards[smask]]).cpu().numpy()
-        words = flat[:4 * n].reshape(n, 4)
+        nw = 4 + (3 if surf else 0)  # per-env words: rows, steps, fail_safe, percent (+ the clip's mean pentration, skate, float)
+        words = flat[:nw * n].reshape(n, nw)
+        flat = flat[nw * n - 4 * n:]  # (what follows is indexed as it always was)
         overflow, n_bad = int(flat[4 * n]), int(flat[4 * n + 1])
         if overflow:
             raise RuntimeError(f"eval_seqs: {overflow} trajectory rows did not fit the record (row_cap {rec.row_cap})")
         if n_bad:
-            raise RuntimeError(f"eval_seqs: {n_bad} recorded expert frame indices lie outside the clip bank")
+            raise RuntimeError(f"eval_seqs: {n_bad} recorded expert frame indices lie outside the clip bank" + (" or recorded body poses are not finite" if surf else ""))
         n_rows, n_steps = words[:, 0].astype(int), words[:, 1].astype(int)
-        W = ql + 72 + 76 + 72 + nm
+        W = ql + 72 + 76 + 72 + nm + (1 if surf else 0)
         rows_h = flat[4 * n + 2:4 * n + 2 + n_rows.sum() * W].reshape(-1, W)
         rew_h = flat[4 * n + 2 + n_rows.sum() * W:]
         r0 = np.concatenate([[0], np.cumsum(n_rows)])
@@ -585,6 +622,9 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
             for i, name in enumerate(EO.METRICS):  # numpy's lengths: T rows, T - 1 for the velocity, T - 2 for the acceleration
                 res[name] = rw[:max(T - (1 if name == "vel_dist" else 2 if name == "accel_dist" else 0), 0), ql + 220 + i].copy()
             res["succ"] = np.array([(not res["fail_safe"]) and res["percent"] == 1])
+            if surf:
+                res["pentration"], res["skate"], res["float"] = (np.float64(words[e, 4 + i]) for i in range(3))
+                res["contact"] = rw[:, ql + 220 + nm].copy()
             out[k] = res
     return out
 

@@ -9,6 +9,9 @@ from ._lib import check, lib
 
 N_BODY = 24
 METRICS = ("root_dist", "vel_dist", "accel_dist", "mpjpe_g", "pa_mpjpe", "mpjpe")  # the order of a row of row_metrics (uhc_eval_metrics.h)
+SURFACE_METRICS = ("pentration", "skate", "float", "contact")  # the order of a row of uhc_surface_metrics' output (uhc_surface_math.h); the reference's spelling
+POSE_ROW, POSE_QUAT = 7 * N_BODY, 3 * N_BODY  # a pose record's row: 72 position doubles, then 96 quaternion doubles
+FRAME_STRIDE, FR_WBPOS, FR_WBQUAT = 584, 151, 223  # the clip bank's frame record (include/uhc_amd.h, uhc_device_env.h)
 
 
 def _p(t):
@@ -22,8 +25,10 @@ def _stream(t):
 class Record:
     """The caller-owned state of uhc_eval_record for n_env envs, zeroed: up to row_cap rows per env."""
 
-    def __init__(self, n_env, row_cap, nqh, device):
+    def __init__(self, n_env, row_cap, nqh, device, poses=False):
         z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=device)
+        # poses: the record also keeps xpos / xquat of bodies 1 .. 24 per row (record_pose), what the surface metrics read
+        self.pred_pose = z(n_env, row_cap, POSE_ROW) if poses else None
         self.n_env, self.row_cap, self.nqh = int(n_env), int(row_cap), int(nqh)
         self.rows, self.steps = z(n_env, dtype=torch.int32), z(n_env, dtype=torch.int32)
         self.pred_qpos, self.pred_jpos = z(n_env, row_cap, nqh), z(n_env, row_cap, 3 * N_BODY)
@@ -67,3 +72,112 @@ def metrics(rec, frames, row_metrics=None, clip_means=None, wait=False):
     check(lib().uhc_eval_metrics(_stream(frames), rec.n_env, N_BODY, rec.nqh, rec.row_cap, _p(rec.rows), _p(rec.pred_qpos), _p(rec.pred_jpos), _p(rec.gt_frame),
                                  _p(frames), frames.shape[0], _p(row_metrics), _p(clip_means), _p(bad), C.byref(h_bad) if wait else None))
     return row_metrics, clip_means, (int(h_bad.value) if wait else bad)
+
+
+def record_pose(rec, phase, xpos, xquat, alive, done=None):
+    """The body poses of the snapshot `record` is about to take: xpos [n_env][3 nbody], xquat [n_env][4 nbody] (the simulation's own fields) of bodies
+    1 .. 24 into row rec.rows[e] of rec.pred_pose, for the envs record's own rule selects.  It reads rec.rows and leaves it alone: call it directly BEFORE
+    record(...) of the same snapshot, on the same stream."""
+    if rec.pred_pose is None:
+        raise ValueError("record_pose: the record keeps no poses (Record(..., poses=True))")
+    n_env = rec.n_env
+    assert xpos.dtype == xquat.dtype == torch.float64 and xpos.is_contiguous() and xquat.is_contiguous() and xpos.shape[0] == xquat.shape[0] == n_env
+    assert xpos.shape[1] % 3 == 0 and xquat.shape[1] == xpos.shape[1] // 3 * 4
+    assert alive.dtype == torch.int32 and alive.is_contiguous() and alive.numel() == n_env
+    if phase == 1:
+        assert done.dtype == torch.int32 and done.is_contiguous() and done.numel() == n_env
+    check(lib().uhc_eval_record_pose(_stream(xpos), int(phase), n_env, xpos.shape[1] // 3, rec.row_cap, _p(xpos), _p(xquat), _p(done), _p(alive), _p(rec.rows),
+                                     _p(rec.pred_pose)))
+
+
+class Surface:
+    """The hull vertices of one or several compiled models that share a topology (the humanoid's bodies 1 .. body_lim - 1, the geoms that own vertices:
+    smpl_eval.surface_tables), on the current device: what uhc_surface_metrics scores poses against.  models: a compiled model, a list of them (index =
+    the clip's body shape), or a list of surface_tables() triples (vert, vert_body, vert_radius).  n_body: the bodies of a pose row (default: 24 for
+    compiled models, the largest body of the triples + 1)."""
+
+    def __init__(self, models, body_lim=N_BODY + 1, n_body=None):
+        import numpy as np
+        from .smpllib.smpl_eval import surface_tables
+        models = list(models) if isinstance(models, (list, tuple)) else [models]
+        if not models:
+            raise ValueError("Surface: no model")
+        compiled = not isinstance(models[0], tuple)
+        tabs = [surface_tables(m, body_lim) if compiled else m for m in models]
+        vert, body, radius = tabs[0]
+        for i, (v, b, r) in enumerate(tabs[1:], 1):
+            if v.shape != vert.shape:
+                raise ValueError(f"Surface: model {i} has {v.shape[0]} hull vertices, model 0 has {vert.shape[0]} (one topology expected)")
+            if not (np.array_equal(b, body) and np.array_equal(r, radius)):  # (the device keeps ONE body and ONE radius table)
+                raise ValueError(f"Surface: model {i} deals its vertices to other bodies, or with other radii, than model 0")
+        self.n_body = int(n_body if n_body is not None else (body_lim - 1 if compiled else int(body.max()) + 1))
+        self.n_vert, self.n_models = int(vert.shape[0]), len(tabs)
+        self.tables = tabs  # (host copies: what hull_vertices takes)
+        vb = np.ascontiguousarray(body, dtype=np.int32)
+        vr = np.ascontiguousarray(radius, dtype=np.float64)
+        vv = np.ascontiguousarray(np.stack([t[0] for t in tabs]), dtype=np.float64)
+        h = C.c_void_p()
+        self._L = lib()
+        check(self._L.uhc_surface_create(self.n_body, self.n_vert, self.n_models, vb.ctypes.data_as(C.c_void_p), vr.ctypes.data_as(C.c_void_p),
+                                         vv.ctypes.data_as(C.c_void_p), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.uhc_surface_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def surface_metrics(surface, pos, quat, seq_start, seq_rows, row_cap=None, seq_model=None, floor_z=0.0, row_out=None, seq_means=None, wait=False):
+    """Penetration, skate, float and contact count of sequences of body poses -> (row_out [n_rows_total][4], seq_means [n_seq][4], bad): SURFACE_METRICS
+    order, mm.  pos [n_rows_total][>= 3 n_body], quat [n_rows_total][>= 4 n_body]: 2-D float64 views with unit inner stride -- columns of a pose record
+    or of the clip bank, read where they lie (their row strides travel); seq_start int64 / seq_rows int32 [n_seq]: first global row and row count of
+    each sequence (clamped to 0 .. row_cap; row_cap None: max(seq_rows), which reads it back); seq_model int32 [n_seq] or None.  Slots of row_out that
+    belong to no row of a sequence keep what they held (NaN in a tensor made here).  bad: an int32 [1] device tensor, or -- wait=True, the call then
+    waits for the stream -- the int itself: rows with a non-finite pose (their values are NaN) plus sequences outside the rows (skipped)."""
+    assert pos.dtype == quat.dtype == torch.float64 and pos.dim() == quat.dim() == 2 and pos.shape[0] == quat.shape[0]
+    assert pos.stride(1) == 1 and quat.stride(1) == 1 and pos.shape[1] >= 3 * surface.n_body and quat.shape[1] >= 4 * surface.n_body
+    assert seq_start.dtype == torch.int64 and seq_rows.dtype == torch.int32 and seq_start.is_contiguous() and seq_rows.is_contiguous()
+    n_seq, n_rows = seq_start.numel(), pos.shape[0]
+    assert seq_rows.numel() == n_seq and (seq_model is None or (seq_model.dtype == torch.int32 and seq_model.is_contiguous() and seq_model.numel() == n_seq))
+    dev = pos.device
+    if row_cap is None:
+        row_cap = max(int(seq_rows.max().item()), 1) if n_seq else 1
+    if row_out is None:
+        row_out = torch.full((n_rows, len(SURFACE_METRICS)), float("nan"), dtype=torch.float64, device=dev)
+    if seq_means is None:
+        seq_means = torch.full((n_seq, len(SURFACE_METRICS)), float("nan"), dtype=torch.float64, device=dev)
+    assert row_out.is_contiguous() and row_out.numel() >= n_rows * len(SURFACE_METRICS) and seq_means.is_contiguous() and seq_means.numel() >= n_seq * len(SURFACE_METRICS)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    h_bad = C.c_int32(0)
+    check(lib().uhc_surface_metrics(_stream(pos), surface._h, n_seq, _p(seq_start), _p(seq_rows), int(row_cap), _p(seq_model), _p(pos), pos.stride(0), _p(quat),
+                                    quat.stride(0), n_rows, float(floor_z), _p(row_out), _p(seq_means), _p(bad), C.byref(h_bad) if wait else None))
+    return row_out, seq_means, (int(h_bad.value) if wait else bad)
+
+
+def surface_metrics_of_record(surface, rec, seq_model=None, **kw):
+    """surface_metrics of every env of a record that keeps poses: sequence e = the rows 0 .. rec.rows[e] - 1 of env e.
+    -> (row_out [n_env][row_cap][4], seq_means [n_env][4], bad)"""
+    if rec.pred_pose is None:
+        raise ValueError("surface_metrics_of_record: the record keeps no poses (Record(..., poses=True))")
+    flat = rec.pred_pose.view(rec.n_env * rec.row_cap, POSE_ROW)
+    start = torch.arange(rec.n_env, dtype=torch.int64, device=flat.device) * rec.row_cap
+    row_out, means, bad = surface_metrics(surface, flat[:, :POSE_QUAT], flat[:, POSE_QUAT:], start, rec.rows, row_cap=rec.row_cap, seq_model=seq_model, **kw)
+    return row_out.view(rec.n_env, rec.row_cap, len(SURFACE_METRICS)), means, bad
+
+
+def surface_metrics_of_bank(surface, frames, clip_start, clip_len, clip_model=None, **kw):
+    """surface_metrics of the expert clips themselves: frames [n_frames][FRAME_STRIDE] (the clip bank), clip_start / clip_len [n_clips] (any integer
+    tensors or sequences), clip_model [n_clips] or None.  -> (row_out [n_frames][4], clip_means [n_clips][4], bad)"""
+    assert frames.dtype == torch.float64 and frames.dim() == 2 and frames.shape[1] == FRAME_STRIDE and frames.is_contiguous()
+    dev = frames.device
+    start = torch.as_tensor(clip_start).to(dev, torch.int64).contiguous()
+    rows = torch.as_tensor(clip_len).to(dev, torch.int32).contiguous()
+    model = None if clip_model is None else torch.as_tensor(clip_model).to(dev, torch.int32).contiguous()
+    return surface_metrics(surface, frames[:, FR_WBPOS:FR_WBPOS + 3 * N_BODY], frames[:, FR_WBQUAT:FR_WBQUAT + 4 * N_BODY], start, rows, seq_model=model, **kw)

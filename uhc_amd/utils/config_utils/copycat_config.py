@@ -108,6 +108,12 @@ class Config(Base_Config):
         self.eval_build = g("eval_build", "host")
         if self.eval_build not in ("host", "device"):
             raise ValueError(f"eval_build: 'host' or 'device', got {self.eval_build!r}")
+        # whether eval_seqs also scores contact quality -- penetration ("pentration", the reference's spelling), skate, float, contact count -- on the models'
+        # hull vertices: with eval_build "device" uhc_eval_record_pose appends the body poses beside every row and ONE uhc_surface_metrics launch scores them;
+        # with "host" the loop also reads xquat and compute_metrics gets hull_vertices.  False (default): eval_seqs returns what it always returned
+        self.eval_surface = g("eval_surface", False)
+        if not isinstance(self.eval_surface, bool):
+            raise ValueError(f"eval_surface: true or false, got {self.eval_surface!r}")
         self.ppo_dtype = g("ppo_dtype", "float64")
         # data-parallel gradient exchange: the dtype on the wire.  float32 (default): SURVEY 8e's 32 MB per optimisation epoch; the local
         # gradient means travel scaled by the rank's sample count and are divided by the global count in the parameters' own float64, so the
