@@ -363,7 +363,9 @@ enum UhcEnvField {
     UHC_E_TARGET_BASE = 9,  /* [n_env][nu] expert joint pose handed to the PD controller */
     UHC_E_CONSUMED = 10,    /* int32 [n_env] 1 where the last uhc_env_auto_reset() started the queued window, 0 elsewhere */
     UHC_E_EPISODE = 11,     /* [2][n_env] running episode length and return (reward + end * end_reward), kept by step / auto_reset */
-    UHC_E_SNAPSHOT = 12     /* [5][n_env] written by uhc_env_auto_reset: done, episode length, episode return, percent, consumed */
+    UHC_E_SNAPSHOT = 12,    /* [5][n_env] written by uhc_env_auto_reset: done, episode length, episode return, percent, consumed */
+    UHC_E_MODEL = 13        /* int32 [n_env] which of the batch's models each env runs on now (assign / auto_reset / a live restart switch it); a batch created
+                             * with ONE model keeps no such array: the field is refused there */
 };
 
 int32_t uhc_env_create(UhcBatch* b, const UhcEnvDesc* desc, UhcEnv** out);
@@ -523,6 +525,34 @@ int32_t uhc_expert_frames(void* stream, int32_t n_body, const int32_t* h_parent,
 int32_t uhc_smpl_qpos(void* stream, int32_t n_joint, const int32_t* h_smpl_to_model, const double* d_root_offset, int32_t n_models,
                       const double* d_pose_aa, const double* d_trans, int64_t n_frames, const int32_t* d_clip_start, const int32_t* d_clip_model,
                       int32_t n_clips, double* d_qpos, double* d_qpos_quat);
+/* uhc_smpl_qpos from 6D rows (smpl_6d_to_qpose, uhc/smpllib/smpl_mujoco.py:776-780): d_full_6d [n_frames][147] = translation | 24 x (column 0, column 1 of the
+ * joint's rotation matrix: process_amass_db.convert_aa_to_orth6d's layout), 8-byte aligned.  Per joint x = a / |a|, z = (x x b) / |x x b|, y = z x x, the
+ * quaternion of that matrix with w >= 0; behind it the same code as uhc_smpl_qpos.  A degenerate pair (a = 0, b parallel to a) gives NaN, as on the host. */
+int32_t uhc_smpl6d_qpos(void* stream, int32_t n_joint, const int32_t* h_smpl_to_model, const double* d_root_offset, int32_t n_models, const double* d_full_6d,
+                        int64_t n_frames, const int32_t* d_clip_start, const int32_t* d_clip_model, int32_t n_clips, double* d_qpos, double* d_qpos_quat);
+
+/* ------------------------------------------------------------------ qpos rows -> SMPL poses on the device
+ * The way back: qpos_to_smpl (uhc/smpllib/smpl_mujoco.py:738-752) and the first half of convert_2_smpl_params (uhc/envs/humanoid_im.py:127-133) as ONE launch
+ * over (row, joint).  Per joint: the hinge triple (Z, Y, X) -> quaternion (scipy's from_euler, intrinsic) or, for the root and for ball joints, the
+ * (w, x, y, z) quaternion normalised (from_quat) -> rotation vector (as_rotvec: w < 0 negates, exactly w == 0 does not; the series at or below 1e-3) and / or the
+ * first two columns of its rotation matrix.  Free function like uhc_smpl_qpos: `stream` is a hipStream_t (NULL = the default stream); every argument is checked
+ * before the first HIP call; n_seq == 0 succeeds and launches nothing; no index or counter, whatever it holds, sends a read or a write outside the arrays.
+ * (Purely additive: UHC_ABI_VERSION stays 11.)
+ *   n_joint 24; h_smpl_to_model [24] (HOST): as for uhc_smpl_qpos; ball: 0 = hinge rows (>= 76 wide: position, root (w, x, y, z), 23 x (Z, Y, X) in model order),
+ *   1 = ball-joint rows (>= 99 wide: position, 24 x (w, x, y, z));
+ *   d_qpos, row_stride: global row g = s * row_cap + r -- row r of sequence s -- lies at d_qpos + g * row_stride (in doubles, >= the width; 8-byte aligned, read
+ *   16 bytes a lane where stride and base allow it).  So one entry point reads the simulation's qpos field (row_cap 1, stride nq), an evaluation record's
+ *   d_pred_qpos ([n_env][row_cap][nqh] with the record's d_rows) and the clip bank's UHC_FR_QPOS columns (stride UHC_FRAME_STRIDE);
+ *   d_seq_rows int32 [n_seq] or NULL (= every row): only rows r < d_seq_rows[s], clamped to 0 .. row_cap, are converted; every other output slot keeps what it held;
+ *   d_seq_model int32 [n_seq] or NULL (= model 0): whose d_root_offset [n_models][3] a sequence's rows lose; an entry outside 0 .. n_models - 1 reads as 0;
+ *   d_root_offset NULL: no offset (count_offset=False);
+ *   d_pose_aa [n_seq * row_cap][72] in SMPL joint order; d_trans [..][3] = qpos[:3] - root_offset; d_full_6d [..][147] = trans | 24 x (column 0, column 1).
+ *   Each may be NULL, not all three; each is 16-byte aligned.
+ *   d_bad int32 [1]: set by the call to the number of converted rows with a quaternion of zero or non-finite norm, or a hinge triple that is not finite (scipy
+ *   raises on a zero quaternion): such a row is NaN in every output.  h_bad (HOST, may be NULL): when given, the call waits for the stream and stores the count. */
+int32_t uhc_qpos_smpl(void* stream, int32_t n_joint, const int32_t* h_smpl_to_model, int32_t ball, const double* d_root_offset, int32_t n_models,
+                      const double* d_qpos, int64_t row_stride, int32_t n_seq, int32_t row_cap, const int32_t* d_seq_rows, const int32_t* d_seq_model,
+                      double* d_pose_aa, double* d_trans, double* d_full_6d, int32_t* d_bad, int32_t* h_bad);
 
 /* ------------------------------------------------------------------ evaluation on the device: trajectory record and imitation metrics
  * Replaces the host half of eval_seq (uhc/agents/agent_copycat.py:438-494: per control step, copies of qpos / xpos / the expert frame / done / reward /

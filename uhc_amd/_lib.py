@@ -23,6 +23,7 @@ SYMBOLS = [
     "uhc_expert_frames", "uhc_eval_record", "uhc_eval_metrics", "uhc_smpl_qpos",
     "uhc_env_live_begin", "uhc_env_live_push", "uhc_env_live_view", "uhc_env_live_end",
     "uhc_surface_create", "uhc_surface_free", "uhc_surface_metrics", "uhc_eval_record_pose",
+    "uhc_qpos_smpl", "uhc_smpl6d_qpos",
 ]
 
 
@@ -111,6 +112,10 @@ def lib():
         L.uhc_surface_metrics.argtypes = [P, P, I, P, P, I, P, P, C.c_int64, P, C.c_int64, C.c_int64, D, P, P, P, C.POINTER(I)]
         L.uhc_eval_record_pose.argtypes = [P, I, I, I, I, P, P, P, P, P, P]
         L.uhc_surface_create.restype = L.uhc_surface_metrics.restype = L.uhc_eval_record_pose.restype = I
+    if hasattr(L, "uhc_qpos_smpl"):  # (additive within ABI 11)
+        L.uhc_qpos_smpl.argtypes = [P, I, C.POINTER(I), I, P, I, P, C.c_int64, I, I, P, P, P, P, P, P, C.POINTER(I)]
+        L.uhc_smpl6d_qpos.argtypes = [P, I, C.POINTER(I), P, I, P, C.c_int64, P, P, I, P, P]
+        L.uhc_qpos_smpl.restype = L.uhc_smpl6d_qpos.restype = I
     _lib = L
     return L
 

@@ -394,9 +394,28 @@ def _eval_policy(self, epoch=0, dump=False):
     return res_dicts
 
 
+def _smpl_params_host(ev, res, model_index):
+    """cfg.eval_smpl on the host: the first half of the reference env's convert_2_smpl_params (uhc/envs/humanoid_im.py:127-133) for one clip's result --
+    qpos_to_smpl of the predicted and the expert rows on the clip's own body shape.  The ball-joint humanoid gets the pred_* pair alone (qpos_quat_to_smpl):
+    the bank keeps the expert's joint quaternions elsewhere than in its qpos columns."""
+    from ..smpllib.smpl_mujoco import qpos_quat_to_smpl, qpos_to_smpl
+    kin = ev.body_models[model_index]
+    if ev.use_quat:
+        pose, trans = qpos_quat_to_smpl(res["pred"], kin)
+        return {"pred_pose_aa": pose.reshape(-1, 72), "pred_trans": trans}
+    out = {}
+    for name in ("pred", "gt"):
+        pose, trans = qpos_to_smpl(res[name], kin, smpl_model=ev.cc_cfg.robot_cfg.get("model", "smpl"))
+        out[name + "_pose_aa"], out[name + "_trans"] = pose.reshape(pose.shape[0], -1), trans
+    return out
+
+
 @torch.no_grad()
 def _eval_seqs(self, take_keys, loader):
-    """Run the mean-action policy over whole clips (eval_seq, agent_copycat.py:438-494), all clips of a chunk at once."""
+    """Run the mean-action policy over whole clips (eval_seq, agent_copycat.py:438-494), all clips of a chunk at once.  With cfg.eval_smpl every clip's
+    result also holds pred_pose_aa (T, 72) / pred_trans (T, 3) and gt_pose_aa / gt_trans, the rows of `pred` and `gt` as SMPL axis-angle poses in SMPL joint
+    order and translations without the body shape's root offset; for the ball-joint humanoid only the pred_* pair (the bank keeps the expert's joint
+    quaternions elsewhere than in its qpos columns)."""
     from ..smpllib.smpl_eval import compute_metrics
     from .. import sim as S
     cfg = self.cfg
@@ -417,6 +436,7 @@ def _eval_seqs(self, take_keys, loader):
     if getattr(cfg, "eval_build", "host") == "device":
         return _eval_seqs_device(self, ev, take_keys, loader, n)
     surf = bool(getattr(cfg, "eval_surface", False))  # contact quality on the hull vertices: the loop also keeps xpos / xquat of bodies 1 .. body_lim - 1
+    smpl = bool(getattr(cfg, "eval_smpl", False))  # the motion handed back as SMPL parameters: pred_pose_aa / pred_trans / gt_pose_aa / gt_trans per clip
     if surf:
         from ..smpllib.smpl_eval import hull_vertices, surface_tables
         tables = [surface_tables(bm, ev.body_lim) for bm in ev.body_models]
@@ -507,6 +527,8 @@ def _eval_seqs(self, take_keys, loader):
                 pz = np.vstack(poses[e])
                 res["pred_vertices"] = hull_vertices(tables[int(clip_model.get(k, 0))], pz[:, :3 * (bl - 1)], pz[:, 3 * (bl - 1):])
             res.update(compute_metrics(res, None))
+            if smpl:
+                res.update(_smpl_params_host(ev, res, int((getattr(self, "_clip_model", None) or {}).get(k, 0))))
             out[k] = res
     return out
 
@@ -534,6 +556,20 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
             with torch.cuda.device(dev):
                 surface = self._eval_surfaces[id(ev)] = EO.Surface(list(ev.body_models), body_lim=ev.body_lim)
         clip_model = getattr(self, "_clip_model", None) or {}
+    smpl = bool(getattr(cfg, "eval_smpl", False))  # the motion as SMPL parameters: one uhc_qpos_smpl launch reads the record, one (once per bank) the bank
+    gt_smpl = None
+    if smpl:
+        clip_model = getattr(self, "_clip_model", None) or {}
+        models = list(ev.body_models)
+        if not ev.use_quat:  # (the ball-joint humanoid's bank keeps the expert's joint quaternions elsewhere: pred_* alone)
+            self._eval_smpl_banks = getattr(self, "_eval_smpl_banks", {})
+            gt_smpl = self._eval_smpl_banks.get(id(ev))
+            if gt_smpl is None or gt_smpl[0] is not frames:
+                with torch.cuda.device(dev):
+                    gp, gt_, gbad = EO.smpl_of_bank(frames, starts, models, clip_model=[int(clip_model.get(k, 0)) for k in ev.clip_keys] if clip_model else None, wait=True)
+                if gbad:
+                    raise RuntimeError(f"eval_seqs: {gbad} expert frames of the clip bank hold a zero or non-finite root quaternion or joint angle")
+                gt_smpl = self._eval_smpl_banks[id(ev)] = (frames, gp, gt_)
     for c0 in range(0, len(take_keys), n):
         keys = take_keys[c0:c0 + n]
         m = len(keys)
@@ -587,17 +623,22 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
             block = 16
 
         row_metrics, _, bad = EO.metrics(rec, frames)
-        if surf:
+        if surf or smpl:
             seq_model = torch.zeros(n, dtype=torch.int32, device=dev)
             seq_model[:m] = torch.tensor([int(clip_model.get(k, 0)) for k in keys], dtype=torch.int32).to(dev)
+        if surf:
             srow, smeans, sbad = EO.surface_metrics_of_record(surface, rec, seq_model=seq_model)
             bad = bad + sbad  # (a non-finite pose: the same refusal below)
+        if smpl:
+            p_pose, p_trans, pbad = EO.smpl_of_record(rec, models, seq_model=seq_model)
+            bad = bad + pbad  # (a recorded quaternion of zero or non-finite norm: the same refusal below)
         # ---- one copy: [per-env words | overflow, bad | every valid row: pred, pred_jpos, gt, gt_jpos, metrics | every reward]
         ar = torch.arange(rec.row_cap, device=dev)[None]
         rmask, smask = ar < rec.rows[:, None], ar < rec.steps[:, None]
         gi = rec.gt_frame[rmask].clamp(0, frames.shape[0] - 1)
         g = frames[gi]
-        rows_d = torch.cat([rec.pred_qpos[rmask], rec.pred_jpos[rmask], g[:, 0:76], g[:, 151:223], row_metrics[rmask]] + ([srow[rmask][:, 3:4]] if surf else []), 1)
+        rows_d = torch.cat([rec.pred_qpos[rmask], rec.pred_jpos[rmask], g[:, 0:76], g[:, 151:223], row_metrics[rmask]] + ([srow[rmask][:, 3:4]] if surf else []) +
+                           ([p_pose[rmask], p_trans[rmask]] if smpl else []) + ([gt_smpl[1][gi], gt_smpl[2][gi]] if gt_smpl else []), 1)
         words = torch.stack([rec.rows.double(), rec.steps.double(), rec.fail_safe.double(), rec.percent] + ([smeans[:, i] for i in range(3)] if surf else []), 1)
         flat = torch.cat([words.reshape(-1), rec.overflow.double(), bad.double(), rows_d.reshape(-1), rec.rewards[smask]]).cpu().numpy()
         nw = 4 + (3 if surf else 0)  # per-env words: rows, steps, fail_safe, percent (+ the clip's mean pentration, skate, float)
@@ -607,9 +648,11 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
         if overflow:
             raise RuntimeError(f"eval_seqs: {overflow} trajectory rows did not fit the record (row_cap {rec.row_cap})")
         if n_bad:
-            raise RuntimeError(f"eval_seqs: {n_bad} recorded expert frame indices lie outside the clip bank" + (" or recorded body poses are not finite" if surf else ""))
+            raise RuntimeError(f"eval_seqs: {n_bad} recorded expert frame indices lie outside the clip bank" + (" or recorded body poses are not finite" if surf else "") +
+                               (" or recorded quaternions cannot be normalised" if smpl else ""))
         n_rows, n_steps = words[:, 0].astype(int), words[:, 1].astype(int)
-        W = ql + 72 + 76 + 72 + nm + (1 if surf else 0)
+        W0 = ql + 72 + 76 + 72 + nm + (1 if surf else 0)  # where the SMPL parameters start: 75 columns for pred, 75 for gt
+        W = W0 + (75 if smpl else 0) + (75 if gt_smpl else 0)
         rows_h = flat[4 * n + 2:4 * n + 2 + n_rows.sum() * W].reshape(-1, W)
         rew_h = flat[4 * n + 2 + n_rows.sum() * W:]
         r0 = np.concatenate([[0], np.cumsum(n_rows)])
@@ -625,6 +668,10 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
             if surf:
                 res["pentration"], res["skate"], res["float"] = (np.float64(words[e, 4 + i]) for i in range(3))
                 res["contact"] = rw[:, ql + 220 + nm].copy()
+            if smpl:
+                res["pred_pose_aa"], res["pred_trans"] = rw[:, W0:W0 + 72].copy(), rw[:, W0 + 72:W0 + 75].copy()
+            if gt_smpl:
+                res["gt_pose_aa"], res["gt_trans"] = rw[:, W0 + 75:W0 + 147].copy(), rw[:, W0 + 147:W0 + 150].copy()
             out[k] = res
     return out
 

@@ -160,6 +160,9 @@ extern "C" int32_t uhc_env_field(UhcEnv* e, int32_t f, void** p, int64_t* n) {
         case UHC_E_CONSUMED: ptr = E.consumed; cnt = N; break;
         case UHC_E_EPISODE: ptr = E.episode; cnt = 2 * N; break;
         case UHC_E_SNAPSHOT: ptr = E.snapshot; cnt = 5 * N; break;
+        case UHC_E_MODEL:
+            if (!E.env_model) return uhc_internal_set_error("uhc_env_field: UHC_E_MODEL: a batch with one model keeps no per-env model");
+            ptr = E.env_model; cnt = N; break;
         default: return uhc_internal_set_error("uhc_env_field: unknown field");
     }
     if (p) *p = ptr;

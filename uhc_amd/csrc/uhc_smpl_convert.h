@@ -10,6 +10,13 @@
 //   uhc_sc_quat_matrix     (x, y, z, w) -> rotation matrix
 //   uhc_sc_root_quat       rotation matrix -> (w, x, y, z) with the reference converter's branch rule: the branch fixes the sign
 //   uhc_sc_row_serial      one frame, the joints as a plain loop: what the device kernel computes with lane = joint
+// The way back (qpos_to_smpl, smpl_mujoco.py; reference :738-752) and the 6D rows (process_amass_db.convert_aa_to_orth6d, smpl_6d_to_qpose), the same way:
+//   uhc_sc_euler_zyx_quat  intrinsic ZYX Euler angles -> (x, y, z, w): Rotation.from_euler("ZYX", .), the three elementary quaternions composed in scipy's order
+//   uhc_sc_quat_unit       Rotation.from_quat's normalisation; a zero or non-finite norm is reported, not divided by
+//   uhc_sc_quat_rotvec     Rotation.as_rotvec: w < 0 negates, the series below 1e-3
+//   uhc_sc_quat_rot6d      (x, y, z, w) -> column 0, then column 1 of the rotation matrix
+//   uhc_sc_rot6d_quat      the two columns -> Gram-Schmidt -> (x, y, z, w) with w >= 0 (Rotation.from_matrix's choice of the largest of m00, m11, m22, trace)
+//   uhc_sc_pose_row_serial one qpos row -> pose_aa / trans / full_6d, the joints as a plain loop
 #pragma once
 #include <math.h>
 
@@ -117,26 +124,157 @@ UHC_SC_HD UhcScV3 uhc_sc_root_pos(const double* trans3, const double* offset3) {
 
 // One frame, the joints as a plain loop.  pose [72]: the rotation vectors in SMPL joint order; slot_of_joint [24]: the model slot SMPL joint j goes to (the
 // inverse of smpl_to_qpose's smpl_2_mujoco table; joint 0 is slot 0).  qpos [76] and / or qpos_quat [99] are written in full, NULL is skipped.
+// SMPL joint j's quaternion into slot m of a 76-wide and / or 99-wide row (NULL is skipped): the part of a row behind the joint's quaternion, whatever it came from
+UHC_SC_HD void uhc_sc_put_joint(const UhcScQuat& q, int j, int m, double* qpos, double* qpos_quat) {
+    if (qpos_quat) {
+        double* o = qpos_quat + 3 + 4 * m;
+        o[0] = q.w, o[1] = q.x, o[2] = q.y, o[3] = q.z;
+    }
+    if (qpos && j == 0) {
+        double R[9];
+        uhc_sc_quat_matrix(q, R);
+        const UhcScQ4 r = uhc_sc_root_quat(R);
+        qpos[3] = r.w, qpos[4] = r.x, qpos[5] = r.y, qpos[6] = r.z;
+    } else if (qpos) {
+        const UhcScEuler e = uhc_sc_quat_euler_zyx(q);
+        double* o = qpos + 7 + 3 * (m - 1);
+        o[0] = e.Z, o[1] = e.Y, o[2] = e.X;
+    }
+}
+
 UHC_SC_HD void uhc_sc_row_serial(const double* pose, const double* trans3, const double* offset3, const int* slot_of_joint, double* qpos, double* qpos_quat) {
     const UhcScV3 p = uhc_sc_root_pos(trans3, offset3);
     if (qpos) qpos[0] = p.x, qpos[1] = p.y, qpos[2] = p.z;
     if (qpos_quat) qpos_quat[0] = p.x, qpos_quat[1] = p.y, qpos_quat[2] = p.z;
+    for (int j = 0; j < UHC_SC_NJ; j++)
+        uhc_sc_put_joint(uhc_sc_rotvec_quat(pose[3 * j], pose[3 * j + 1], pose[3 * j + 2]), j, slot_of_joint[j], qpos, qpos_quat);
+}
+
+// ------------------------------------------------------------------ qpos rows -> SMPL poses, and the 6D rows
+#define UHC_SC_N6D 147  // a 6D row: translation, 24 x (column 0, column 1 of the rotation matrix)
+
+struct UhcScRot6 {
+    double ax, ay, az, bx, by, bz;  // column 0, column 1
+};
+
+// scipy's _compose_quat: the product p * q, the cross product formed first
+UHC_SC_HD UhcScQuat uhc_sc_quat_mul(const UhcScQuat& p, const UhcScQuat& q) {
+    const double cx = p.y * q.z - p.z * q.y, cy = p.z * q.x - p.x * q.z, cz = p.x * q.y - p.y * q.x;
+    return {p.w * q.x + q.w * p.x + cx, p.w * q.y + q.w * p.y + cy, p.w * q.z + q.w * p.z + cz, p.w * q.w - p.x * q.x - p.y * q.y - p.z * q.z};
+}
+
+// Rotation.from_euler("ZYX", (Z, Y, X)), intrinsic: ((qz * qy) * qx), each an elementary quaternion (sin, cos of the half angle); not normalised, no canonical sign
+UHC_SC_HD UhcScQuat uhc_sc_euler_zyx_quat(double Z, double Y, double X) {
+    const UhcScQuat qz = {0.0, 0.0, sin(Z / 2.0), cos(Z / 2.0)}, qy = {0.0, sin(Y / 2.0), 0.0, cos(Y / 2.0)}, qx = {sin(X / 2.0), 0.0, 0.0, cos(X / 2.0)};
+    return uhc_sc_quat_mul(uhc_sc_quat_mul(qz, qy), qx);
+}
+
+UHC_SC_HD bool uhc_sc_finite(double v) { return v - v == 0.0; }  // (false for NaN and +-inf; no <cmath> overload question between host and device)
+
+// Rotation.from_quat: q / |q|.  false: the norm is zero or not finite (scipy raises on zero) and q is left as it is
+UHC_SC_HD bool uhc_sc_quat_unit(UhcScQuat& q) {
+    const double n = sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    if (!(n > 0.0) || !uhc_sc_finite(n)) return false;
+    q = {q.x / n, q.y / n, q.z / n, q.w / n};
+    return true;
+}
+
+// Rotation.as_rotvec: the quaternion with w < 0 is negated (w == 0 is not), angle = 2 atan2(|xyz|, w); at or below 1e-3 the series of angle / sin(angle / 2)
+UHC_SC_HD UhcScV3 uhc_sc_quat_rotvec(const UhcScQuat& q0) {
+    const UhcScQuat q = q0.w < 0.0 ? UhcScQuat{-q0.x, -q0.y, -q0.z, -q0.w} : q0;
+    const double angle = 2.0 * atan2(sqrt(q.x * q.x + q.y * q.y + q.z * q.z), q.w);
+    double scale;
+    if (angle <= 1e-3) {
+        const double angle2 = angle * angle;
+        scale = 2.0 + angle2 / 12.0 + 7.0 * angle2 * angle2 / 2880.0;
+    } else {
+        scale = angle / sin(angle / 2.0);
+    }
+    return {scale * q.x, scale * q.y, scale * q.z};
+}
+
+// convert_aa_to_orth6d in float64: column 0, then column 1 of Rotation.as_matrix
+UHC_SC_HD UhcScRot6 uhc_sc_quat_rot6d(const UhcScQuat& q) {
+    double R[9];
+    uhc_sc_quat_matrix(q, R);
+    return {R[0], R[3], R[6], R[1], R[4], R[7]};
+}
+
+// smpl_6d_to_qpose: x = a / |a|, z = (x x b) / |x x b|, y = z x x, the matrix with those COLUMNS, then Rotation.from_matrix's quaternion: the largest of
+// (m00, m11, m22, trace) picks the formula, the result is normalised.  The host goes on through as_rotvec and from_rotvec, whose quaternion has w >= 0: so has this.
+UHC_SC_HD UhcScQuat uhc_sc_rot6d_quat(const UhcScRot6& r) {
+    const double na = sqrt(r.ax * r.ax + r.ay * r.ay + r.az * r.az);
+    const double xx = r.ax / na, xy = r.ay / na, xz = r.az / na;
+    double zx = xy * r.bz - xz * r.by, zy = xz * r.bx - xx * r.bz, zz = xx * r.by - xy * r.bx;
+    const double nz = sqrt(zx * zx + zy * zy + zz * zz);
+    zx = zx / nz, zy = zy / nz, zz = zz / nz;
+    const double yx = zy * xz - zz * xy, yy = zz * xx - zx * xz, yz = zx * xy - zy * xx;
+    // row-major R = [x y z] as columns: m00 = xx, m01 = yx, m02 = zx; m10 = xy, m11 = yy, m12 = zy; m20 = xz, m21 = yz, m22 = zz
+    const double m00 = xx, m11 = yy, m22 = zz, tr = m00 + m11 + m22;
+    UhcScQuat q;
+    if (tr >= m00 && tr >= m11 && tr >= m22) {
+        q = {yz - zy, zx - xz, xy - yx, 1.0 + tr};
+    } else if (m00 >= m11 && m00 >= m22) {
+        q = {1.0 - tr + 2.0 * m00, xy + yx, xz + zx, yz - zy};
+    } else if (m11 >= m22) {
+        q = {yx + xy, 1.0 - tr + 2.0 * m11, yz + zy, zx - xz};
+    } else {
+        q = {xz + zx, zy + yz, 1.0 - tr + 2.0 * m22, xy - yx};
+    }
+    const double n = sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    q = {q.x / n, q.y / n, q.z / n, q.w / n};
+    return q.w < 0.0 ? UhcScQuat{-q.x, -q.y, -q.z, -q.w} : q;
+}
+
+// SMPL joint j of one qpos row as a unit quaternion (x, y, z, w); m: the joint's model slot.  Hinge rows (width >= 76): position, root (w, x, y, z), 23 x (Z, Y, X);
+// ball-joint rows (width >= 99): position, 24 x (w, x, y, z).  false: a quaternion of zero or non-finite norm, or a hinge triple that is not finite.
+UHC_SC_HD bool uhc_sc_row_joint_quat(const double* row, int ball, int j, int m, UhcScQuat& q) {
+    if (ball || j == 0) {
+        const double* p = row + 3 + 4 * m;  // (the root is slot 0 in both layouts)
+        q = {p[1], p[2], p[3], p[0]};
+        return uhc_sc_quat_unit(q);
+    }
+    const double* p = row + 7 + 3 * (m - 1);
+    q = uhc_sc_euler_zyx_quat(p[0], p[1], p[2]);
+    return uhc_sc_finite(q.x + q.y + q.z + q.w);
+}
+
+// One qpos row, the joints as a plain loop: pose_aa [72] in SMPL joint order, trans [3] = row[:3] - offset3 (NULL: no offset), full_6d [147] = trans | 24 x 6;
+// NULL is skipped.  Returns 1 for a bad row (uhc_sc_row_joint_quat refused a joint): every output given is NaN throughout.
+UHC_SC_HD int uhc_sc_pose_row_serial(const double* row, int ball, const double* offset3, const int* slot_of_joint, double* pose_aa, double* trans3, double* full_6d) {
+    const UhcScV3 t = {row[0] - (offset3 ? offset3[0] : 0.0), row[1] - (offset3 ? offset3[1] : 0.0), row[2] - (offset3 ? offset3[2] : 0.0)};
+    if (trans3) trans3[0] = t.x, trans3[1] = t.y, trans3[2] = t.z;
+    if (full_6d) full_6d[0] = t.x, full_6d[1] = t.y, full_6d[2] = t.z;
+    int bad = 0;
     for (int j = 0; j < UHC_SC_NJ; j++) {
-        const UhcScQuat q = uhc_sc_rotvec_quat(pose[3 * j], pose[3 * j + 1], pose[3 * j + 2]);
-        const int m = slot_of_joint[j];
-        if (qpos_quat) {
-            double* o = qpos_quat + 3 + 4 * m;
-            o[0] = q.w, o[1] = q.x, o[2] = q.y, o[3] = q.z;
+        UhcScQuat q;
+        if (!uhc_sc_row_joint_quat(row, ball, j, slot_of_joint[j], q)) bad = 1;
+        if (pose_aa) {
+            const UhcScV3 r = uhc_sc_quat_rotvec(q);
+            pose_aa[3 * j] = r.x, pose_aa[3 * j + 1] = r.y, pose_aa[3 * j + 2] = r.z;
         }
-        if (qpos && j == 0) {
-            double R[9];
-            uhc_sc_quat_matrix(q, R);
-            const UhcScQ4 r = uhc_sc_root_quat(R);
-            qpos[3] = r.w, qpos[4] = r.x, qpos[5] = r.y, qpos[6] = r.z;
-        } else if (qpos) {
-            const UhcScEuler e = uhc_sc_quat_euler_zyx(q);
-            double* o = qpos + 7 + 3 * (m - 1);
-            o[0] = e.Z, o[1] = e.Y, o[2] = e.X;
+        if (full_6d) {
+            const UhcScRot6 s = uhc_sc_quat_rot6d(q);
+            double* o = full_6d + 3 + 6 * j;
+            o[0] = s.ax, o[1] = s.ay, o[2] = s.az, o[3] = s.bx, o[4] = s.by, o[5] = s.bz;
         }
+    }
+    if (bad) {
+        const double nan = NAN;
+        for (int k = 0; pose_aa && k < 3 * UHC_SC_NJ; k++) pose_aa[k] = nan;
+        for (int k = 0; trans3 && k < 3; k++) trans3[k] = nan;
+        for (int k = 0; full_6d && k < UHC_SC_N6D; k++) full_6d[k] = nan;
+    }
+    return bad;
+}
+
+// One 6D row -> qpos [76] and / or qpos_quat [99]: uhc_sc_row_serial's body behind uhc_sc_rot6d_quat (what smpl_6d_to_qpose computes through smpl_to_qpose)
+UHC_SC_HD void uhc_sc_row6d_serial(const double* full_6d, const double* offset3, const int* slot_of_joint, double* qpos, double* qpos_quat) {
+    const UhcScV3 p = uhc_sc_root_pos(full_6d, offset3);
+    if (qpos) qpos[0] = p.x, qpos[1] = p.y, qpos[2] = p.z;
+    if (qpos_quat) qpos_quat[0] = p.x, qpos_quat[1] = p.y, qpos_quat[2] = p.z;
+    for (int j = 0; j < UHC_SC_NJ; j++) {
+        const double* s = full_6d + 3 + 6 * j;
+        uhc_sc_put_joint(uhc_sc_rot6d_quat({s[0], s[1], s[2], s[3], s[4], s[5]}), j, slot_of_joint[j], qpos, qpos_quat);
     }
 }

@@ -308,6 +308,44 @@ class VecHumanoidEnv:
             self.env.live_push(env_ids, got[0], restart=restart, root_quat_record=got[1][:, 3:7] if self.use_quat else None,
                                model=None if cm is None else torch.tensor(cm, dtype=torch.int32))
 
+    def live_push_6d(self, env_ids, full_6d, restart=None, model=None):
+        """live_push from 6D rows, what the reference's kinematic policies emit: full_6d (n, 147) = translation | 24 x (column 0, column 1 of the joint's
+        rotation matrix) -> uhc_smpl6d_qpos -> uhc_env_live_push; no row visits the host.  model: as for live_push_smpl."""
+        if self.cc_cfg.robot_cfg.get("model", "smpl") != "smpl":
+            raise NotImplementedError("only the options the copycat path uses are built (SURVEY.md 8f-4)")
+        n = int(torch.as_tensor(full_6d).shape[0])
+        if n == 0:
+            return
+        cm = None if model is None else [int(m) for m in model]
+        with torch.cuda.device(self.device):
+            got = S.smpl6d_qpos_device(full_6d, np.arange(n), list(self.body_models), clip_model=cm, count_offset=self.cc_cfg.robot_cfg.get("mesh", True),
+                                       want=("qpos", "qpos_quat") if self.use_quat else ("qpos",), device=self.device)
+            self.env.live_push(env_ids, got[0], restart=restart, root_quat_record=got[1][:, 3:7] if self.use_quat else None,
+                               model=None if cm is None else torch.tensor(cm, dtype=torch.int32))
+
+    def smpl_pose(self, want=("pose_aa", "trans")):
+        """The current state of every env as SMPL parameters -- the first half of the reference env's convert_2_smpl_params (humanoid_im.py:127-133):
+        pose_aa (n_env, 72) in SMPL joint order, trans (n_env, 3) = root position - the root offset of the env's OWN body shape; want may also name
+        "full_6d" (n_env, 147) = trans | 24 x (column 0, column 1 of the rotation matrix).  ONE launch (uhc_qpos_smpl) on the simulation's qpos field where
+        it lies -- hinge or ball-joint rows, objects behind the humanoid or not --, no readback.  Returns tensors the env owns and writes again at the next
+        call, in the order of `want`.  A state with a zero or non-finite quaternion comes out as NaN."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or len(set(want)) != len(want) or any(w not in S.POSE_WIDTHS for w in want):
+            raise ValueError(f"smpl_pose: want names 'pose_aa', 'trans' and / or 'full_6d', got {want!r}")
+        if self.cc_cfg.robot_cfg.get("model", "smpl") != "smpl":
+            raise NotImplementedError("smpl_pose: only the 24-joint SMPL layout is built on the device (qpos_to_smpl converts SMPL-H on the host)")
+        with torch.cuda.device(self.device):
+            op = getattr(self, "_smpl_op", None)
+            if op is None:
+                op = self._smpl_op = S.SmplPoseOp(list(self.body_models), self.device, count_offset=True)
+                self._smpl_out = {}
+                self._smpl_model = self.env.field(S.E_MODEL) if len(self.body_models) > 1 else None  # the batch's own per-env selector, read where it lies
+            for w in want:
+                if w not in self._smpl_out:
+                    self._smpl_out[w] = torch.full((self.n_env, S.POSE_WIDTHS[w]), float("nan"), dtype=torch.float64, device=self.device)
+            op(self.sim.field(S.F_QPOS), self.n_env, 1, None, self._smpl_model, {w: self._smpl_out[w] for w in want})
+        return tuple(self._smpl_out[w] for w in want)
+
     def live_view(self):
         return self.env.live_view()
 

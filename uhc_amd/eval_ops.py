@@ -172,6 +172,32 @@ def surface_metrics_of_record(surface, rec, seq_model=None, **kw):
     return row_out.view(rec.n_env, rec.row_cap, len(SURFACE_METRICS)), means, bad
 
 
+def smpl_of_record(rec, models, seq_model=None, want=("pose_aa", "trans"), wait=False):
+    """The recorded motion of every env as SMPL parameters (uhc_qpos_smpl, sim.qpos_smpl_device): rec.pred_qpos is read where it lies, rec.rows are the row
+    counts.  models: the compiled model(s) of the humanoid (hinge or ball-joint), seq_model int32 [n_env] or None: each env's body shape.
+    -> the tensors of `want` ([n_env][row_cap][72 / 3 / 147]; slots beyond an env's rows are NaN), then bad as qpos_smpl_device returns it."""
+    from .sim import qpos_smpl_device
+    return qpos_smpl_device(rec.pred_qpos, models, seq_rows=rec.rows, seq_model=seq_model, want=want, wait=wait)
+
+
+def smpl_of_bank(frames, clip_start, models, clip_model=None, want=("pose_aa", "trans"), wait=False):
+    """The expert clips themselves as SMPL parameters, from the qpos columns of the bank (hinge rows: the bank of the ball-joint humanoid keeps its joint
+    quaternions elsewhere and is not served).  frames [n_frames][FRAME_STRIDE]; clip_start [n_clips] (any integer tensor or sequence, ascending from 0) and
+    clip_model [n_clips] or None: which body shape's root offset a clip's frames lose.  -> the tensors of `want` ([n_frames][72 / 3 / 147]), then bad."""
+    from .sim import qpos_smpl_device
+    assert frames.dtype == torch.float64 and frames.dim() == 2 and frames.shape[1] == FRAME_STRIDE and frames.is_contiguous()
+    ms = list(models) if isinstance(models, (list, tuple)) else [models]
+    if int(ms[0].nq) != int(ms[0].nv) + 1:
+        raise NotImplementedError("smpl_of_bank: the bank's qpos columns are hinge rows; the ball-joint humanoid's joint quaternions are not among them")
+    dev = frames.device
+    row_model = None
+    if clip_model is not None and frames.shape[0]:  # every frame is a sequence of one row: the frame's model is its clip's
+        start = torch.as_tensor(clip_start).to(dev, torch.int64).contiguous()
+        clip_of = torch.searchsorted(start, torch.arange(frames.shape[0], device=dev), right=True) - 1
+        row_model = torch.as_tensor(clip_model).to(dev, torch.int32)[clip_of.clamp_(0, start.numel() - 1)].contiguous()
+    return qpos_smpl_device(frames[:, 0:76], ms, seq_model=row_model, want=want, wait=wait)
+
+
 def surface_metrics_of_bank(surface, frames, clip_start, clip_len, clip_model=None, **kw):
     """surface_metrics of the expert clips themselves: frames [n_frames][FRAME_STRIDE] (the clip bank), clip_start / clip_len [n_clips] (any integer
     tensors or sequences), clip_model [n_clips] or None.  -> (row_out [n_frames][4], clip_means [n_clips][4], bad)"""

@@ -197,9 +197,9 @@ class SimBatch:
         return m.value
 
 
-E_OBS, E_REWARD, E_REWARD_PARTS, E_DONE, E_FAIL, E_END, E_PERCENT, E_CUR_T, E_BODY_DIFF, E_TARGET_BASE, E_CONSUMED, E_EPISODE, E_SNAPSHOT = range(13)
+E_OBS, E_REWARD, E_REWARD_PARTS, E_DONE, E_FAIL, E_END, E_PERCENT, E_CUR_T, E_BODY_DIFF, E_TARGET_BASE, E_CONSUMED, E_EPISODE, E_SNAPSHOT, E_MODEL = range(14)
 _E_ROWS = {E_EPISODE: 2, E_SNAPSHOT: 5}  # fields laid out [rows][n_env]
-_E_INT = {E_DONE, E_FAIL, E_END, E_CUR_T, E_CONSUMED}
+_E_INT = {E_DONE, E_FAIL, E_END, E_CUR_T, E_CONSUMED, E_MODEL}
 FRAME_STRIDE = 584
 FR = dict(qpos=(0, 76), qvel=(76, 75), wbpos=(151, 72), wbquat=(223, 96), bquat=(319, 96), bangvel=(415, 72), ee_wpos=(487, 15), com=(502, 3), body_com=(512, 72))
 
@@ -288,7 +288,6 @@ def smpl_qpos_device(pose_aa, trans, clip_start, models, clip_model=None, count_
       once and added to the root position when count_offset --, clip_model: which of them each clip is converted for (None: the first for every
       clip); want: ("qpos",), ("qpos_quat",) or both -- the hinge humanoid's 76-wide rows, the ball-joint humanoid's 99-wide rows.
     Returns the float64 device tensors in the order of `want`; they go into `expert_frames_device` as they are."""
-    from .smpllib.smpl_mujoco import smpl_to_model_table
     if not torch.cuda.is_available():
         raise RuntimeError("uhc_amd.sim.smpl_qpos_device needs an MI355X (torch.cuda unavailable); there is no CPU fallback")
     ms = list(models) if isinstance(models, (list, tuple)) else [models]
@@ -298,13 +297,7 @@ def smpl_qpos_device(pose_aa, trans, clip_start, models, clip_model=None, count_
     if device is None:
         device = pose_aa.device if isinstance(pose_aa, torch.Tensor) and pose_aa.is_cuda else torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
-    tables = [smpl_to_model_table(m) for m in ms]
-    if any(t != tables[0] for t in tables[1:]):
-        raise ValueError("smpl_qpos_device: every body shape must share the first one's body order")
-    s2m = np.ascontiguousarray(tables[0], dtype=np.int32)
-    if s2m.shape != (24,):
-        raise ValueError(f"smpl_qpos_device: the model carries {s2m.size} of the 24 SMPL bodies")
-    cs = np.asarray(clip_start.cpu() if isinstance(clip_start, torch.Tensor) else clip_start, dtype=np.int64).reshape(-1)
+    s2m = _smpl_table(ms, "smpl_qpos_device")
     pose = torch.as_tensor(pose_aa)
     n_frames = int(pose.shape[0])
     if pose.ndim < 2 or pose.numel() != n_frames * 72:
@@ -314,13 +307,7 @@ def smpl_qpos_device(pose_aa, trans, clip_start, models, clip_model=None, count_
         trans = torch.as_tensor(trans)
         if tuple(trans.shape) != (n_frames, 3):
             raise ValueError(f"smpl_qpos_device: trans must be ({n_frames}, 3), got {tuple(trans.shape)}")
-    if cs.size == 0 or cs[0] != 0 or np.any(np.diff(cs) <= 0) or (n_frames and cs[-1] >= n_frames):
-        raise ValueError("smpl_qpos_device: clip_start must ascend strictly from 0 and stay below n_frames")
-    cm = None
-    if clip_model is not None:
-        cm = np.asarray(clip_model.cpu() if isinstance(clip_model, torch.Tensor) else clip_model, dtype=np.int64).reshape(-1)
-        if cm.shape != cs.shape or cm.min() < 0 or cm.max() >= len(ms):
-            raise ValueError(f"smpl_qpos_device: clip_model must name one of the {len(ms)} body shapes for each of the {cs.size} clips")
+    cs, cm = _clip_tables("smpl_qpos_device", clip_start, clip_model, n_frames, len(ms))
     widths = dict(qpos=76, qpos_quat=99)
     with torch.cuda.device(device):  # (the temporaries below are freed in stream order: the launch is on torch's current stream)
         out = {w: torch.empty((n_frames, widths[w]), dtype=torch.float64, device=device) for w in want}
@@ -334,6 +321,137 @@ def smpl_qpos_device(pose_aa, trans, clip_start, models, clip_model=None, count_
             check(lib().uhc_smpl_qpos(C.c_void_p(torch.cuda.current_stream(device).cuda_stream), 24, s2m.ctypes.data_as(C.POINTER(C.c_int32)), ptr(off), len(ms),
                                       ptr(p), ptr(t), n_frames, ptr(d_cs), ptr(d_cm), int(cs.size), ptr(out.get("qpos")), ptr(out.get("qpos_quat"))))
     return tuple(out[w] for w in want)
+
+
+def _clip_tables(who, clip_start, clip_model, n_frames, n_models):
+    """-> (clip_start, clip_model or None) as int64 host arrays, checked: the starts ascend strictly from 0 below n_frames, the models are in range"""
+    cs = np.asarray(clip_start.cpu() if isinstance(clip_start, torch.Tensor) else clip_start, dtype=np.int64).reshape(-1)
+    if cs.size == 0 or cs[0] != 0 or np.any(np.diff(cs) <= 0) or (n_frames and cs[-1] >= n_frames):
+        raise ValueError(f"{who}: clip_start must ascend strictly from 0 and stay below n_frames")
+    cm = None
+    if clip_model is not None:
+        cm = np.asarray(clip_model.cpu() if isinstance(clip_model, torch.Tensor) else clip_model, dtype=np.int64).reshape(-1)
+        if cm.shape != cs.shape or cm.min() < 0 or cm.max() >= n_models:
+            raise ValueError(f"{who}: clip_model must name one of the {n_models} body shapes for each of the {cs.size} clips")
+    return cs, cm
+
+
+def _smpl_table(ms, who):
+    from .smpllib.smpl_mujoco import smpl_to_model_table
+    tables = [smpl_to_model_table(m) for m in ms]
+    if any(t != tables[0] for t in tables[1:]):
+        raise ValueError(f"{who}: every body shape must share the first one's body order")
+    s2m = np.ascontiguousarray(tables[0], dtype=np.int32)
+    if s2m.shape != (24,):
+        raise ValueError(f"{who}: the model carries {s2m.size} of the 24 SMPL bodies")
+    return s2m
+
+
+def smpl6d_qpos_device(full_6d, clip_start, models, clip_model=None, count_offset: bool = True, want=("qpos",), device=None):
+    """6D rows -> qpos rows on the device (uhc_smpl6d_qpos): what `smpl_6d_to_qpose(clip, model)`, clip by clip, gives on the host.  The mirror of
+    `smpl_qpos_device`: full_6d (n_frames, 147) = translation | 24 x (column 0, column 1 of the joint's rotation matrix); every other argument and the
+    result as there."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("uhc_amd.sim.smpl6d_qpos_device needs an MI355X (torch.cuda unavailable); there is no CPU fallback")
+    ms = list(models) if isinstance(models, (list, tuple)) else [models]
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in ("qpos", "qpos_quat") for w in want):
+        raise ValueError(f"smpl6d_qpos_device: want names 'qpos' and / or 'qpos_quat', got {want!r}")
+    if device is None:
+        device = full_6d.device if isinstance(full_6d, torch.Tensor) and full_6d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    s2m = _smpl_table(ms, "smpl6d_qpos_device")
+    full = torch.as_tensor(full_6d)
+    n_frames = int(full.shape[0])
+    if full.ndim != 2 or full.shape[1] != 147:
+        raise ValueError(f"smpl6d_qpos_device: full_6d must be (n_frames, 147), got {tuple(full.shape)}")
+    cs, cm = _clip_tables("smpl6d_qpos_device", clip_start, clip_model, n_frames, len(ms))
+    widths = dict(qpos=76, qpos_quat=99)
+    with torch.cuda.device(device):  # (the temporaries below are freed in stream order: the launch is on torch's current stream)
+        out = {w: torch.empty((n_frames, widths[w]), dtype=torch.float64, device=device) for w in want}
+        if n_frames:
+            off = torch.from_numpy(np.stack([np.asarray(m.body_pos, dtype=np.float64)[1] for m in ms])).to(device).contiguous() if count_offset else None
+            p = full.to(device, torch.float64).contiguous()
+            d_cs = torch.from_numpy(cs.astype(np.int32)).to(device)
+            d_cm = None if cm is None else torch.from_numpy(cm.astype(np.int32)).to(device)
+            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+            check(lib().uhc_smpl6d_qpos(C.c_void_p(torch.cuda.current_stream(device).cuda_stream), 24, s2m.ctypes.data_as(C.POINTER(C.c_int32)), ptr(off), len(ms),
+                                        ptr(p), n_frames, ptr(d_cs), ptr(d_cm), int(cs.size), ptr(out.get("qpos")), ptr(out.get("qpos_quat"))))
+    return tuple(out[w] for w in want)
+
+
+POSE_WIDTHS = dict(pose_aa=72, trans=3, full_6d=147)
+
+
+class SmplPoseOp:
+    """What a `qpos_smpl_device` call needs of the models -- the joint table and the root offsets on the device -- kept, for callers that convert every
+    control step (VecHumanoidEnv.smpl_pose): the call is then ONE launch, no upload and no allocation."""
+
+    def __init__(self, models, device, count_offset=True):
+        self.ms = list(models) if isinstance(models, (list, tuple)) else [models]
+        self.device = torch.device(device)
+        self.s2m = _smpl_table(self.ms, "qpos_smpl_device")
+        self.ball = bool(int(self.ms[0].nq) != int(self.ms[0].nv) + 1)
+        self.width = 99 if self.ball else 76
+        self.off = torch.from_numpy(np.stack([np.asarray(m.body_pos, dtype=np.float64)[1] for m in self.ms])).to(self.device).contiguous() if count_offset else None
+        self.bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def __call__(self, rows, n_seq, row_cap, seq_rows, seq_model, out, wait=False):
+        """rows: a float64 device tensor whose rows of >= width doubles lie rows.stride(-2) apart; out: {name: contiguous tensor of n_seq * row_cap rows}"""
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        h_bad = C.c_int32(0)
+        check(lib().uhc_qpos_smpl(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), 24, self.s2m.ctypes.data_as(C.POINTER(C.c_int32)), int(self.ball),
+                                  ptr(self.off), len(self.ms), ptr(rows), int(rows.stride(-2)), int(n_seq), int(row_cap), ptr(seq_rows), ptr(seq_model),
+                                  ptr(out.get("pose_aa")), ptr(out.get("trans")), ptr(out.get("full_6d")), ptr(self.bad), C.byref(h_bad) if wait else None))
+        return int(h_bad.value) if wait else self.bad
+
+
+def qpos_smpl_device(qpos, models, seq_rows=None, seq_model=None, count_offset: bool = True, want=("pose_aa", "trans"), out=None, wait=False):
+    """qpos rows -> SMPL poses on the device (uhc_qpos_smpl): what `qpos_to_smpl(rows, model)` -- for the ball-joint humanoid `qpos_quat_to_smpl` -- gives
+    on the host, from ONE launch on torch's current stream.
+      qpos: (n_rows, w) or (n_seq, row_cap, w), float64 with unit inner stride; a device tensor is read where it lies, whatever its row stride (the
+      simulation's qpos field with objects behind the humanoid, an evaluation record's pred_qpos, the qpos columns of the clip bank); anything else is uploaded.
+      The rows are hinge rows (w >= 76) or, when the models are ball-joint models, ball-joint rows (w >= 99);
+      models: one compiled `Model` (or a list of them, same body order) per body shape -- their root offsets (body_pos[1]) are subtracted from the root
+      position when count_offset --, seq_model int32 (n_seq,) or None: which of them each sequence (each row of a 2-D qpos) is converted for; an entry out of
+      range reads as 0; seq_rows int32 (n_seq,) or None: only the first seq_rows[s] rows (clamped to 0 .. row_cap) of sequence s are converted, every other
+      output slot keeps what it held (NaN in a tensor made here);
+      want: any of "pose_aa" (.., 72) in SMPL joint order, "trans" (.., 3), "full_6d" (.., 147) = trans | 24 x (column 0, column 1 of the rotation matrix);
+      out: {name: tensor} to write into.
+    Returns the float64 device tensors in the order of `want`, then `bad`: an int32 [1] device tensor, or -- wait=True, the call then waits for the stream --
+    the int itself: the number of rows with a quaternion of zero or non-finite norm (scipy raises there); they are NaN throughout."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in POSE_WIDTHS for w in want):
+        raise ValueError(f"qpos_smpl_device: want names 'pose_aa', 'trans' and / or 'full_6d', got {want!r}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("uhc_amd.sim.qpos_smpl_device needs an MI355X (torch.cuda unavailable); there is no CPU fallback")
+    device = qpos.device if isinstance(qpos, torch.Tensor) and qpos.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(device):
+        op = SmplPoseOp(models, device, count_offset)
+        rows = torch.as_tensor(qpos)
+        if not (rows.is_cuda and rows.dtype == torch.float64):
+            rows = rows.to(device, torch.float64).contiguous()
+        if rows.ndim not in (2, 3) or rows.shape[-1] < op.width:
+            raise ValueError(f"qpos_smpl_device: qpos must be (n_rows, >= {op.width}) or (n_seq, row_cap, >= {op.width}), got {tuple(rows.shape)}")
+        n_seq, row_cap = (int(rows.shape[0]), 1) if rows.ndim == 2 else (int(rows.shape[0]), int(rows.shape[1]))
+        lead = tuple(rows.shape[:-1])
+        if rows.numel() and (rows.stride(-1) != 1 or (rows.ndim == 3 and rows.stride(0) != row_cap * rows.stride(1))):
+            raise ValueError("qpos_smpl_device: qpos rows must have unit inner stride and lie one row stride apart")
+        for name, t in (("seq_rows", seq_rows), ("seq_model", seq_model)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n_seq):
+                raise ValueError(f"qpos_smpl_device: {name} must be a contiguous int32 device tensor of {n_seq} entries")
+        res = {}
+        for w in want:
+            t = None if out is None else out.get(w)
+            if t is None:
+                t = torch.full(lead + (POSE_WIDTHS[w],), float("nan"), dtype=torch.float64, device=device)
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n_seq * row_cap * POSE_WIDTHS[w]):
+                raise ValueError(f"qpos_smpl_device: out[{w!r}] must be a contiguous float64 device tensor of {n_seq * row_cap} x {POSE_WIDTHS[w]}")
+            res[w] = t
+        if n_seq * row_cap == 0:
+            return tuple(res[w] for w in want) + ((0 if wait else op.bad),)
+        bad = op(rows, n_seq, row_cap, seq_rows, seq_model, res, wait=wait)
+    return tuple(res[w] for w in want) + (bad,)
 
 
 class EnvBatch:

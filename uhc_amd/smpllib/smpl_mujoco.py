@@ -218,6 +218,38 @@ def qpos_to_smpl(qpos, mj_model, smpl_model="smpl"):
     return pose, qpos[:, :3] - np.asarray(mj_model.body_pos)[1]
 
 
+def qpos_quat_to_smpl(qpos_quat, mj_model):
+    """`qpos_to_smpl` for the ball-joint humanoid's rows: qpos_quat (T, >= 99) = root position | 24 x (w, x, y, z) in the model's body order ->
+    (pose_aa (T, 24, 3) in SMPL joint order, trans (T, 3)).  Per joint from_quat (which normalises, and raises on a zero quaternion), then as_rotvec."""
+    from scipy.spatial.transform import Rotation as sRot
+    qpos_quat = np.asarray(qpos_quat, dtype=np.float64)
+    s2m = smpl_to_model_table(mj_model)
+    pose = np.zeros((qpos_quat.shape[0], 24, 3))
+    for m, j in enumerate(s2m):
+        pose[:, j] = sRot.from_quat(qpos_quat[:, 3 + 4 * m:7 + 4 * m][:, [1, 2, 3, 0]]).as_rotvec()
+    return pose, qpos_quat[:, :3] - np.asarray(mj_model.body_pos)[1]
+
+
+def qpos_to_smpl_device(qpos, mj_model, smpl_model="smpl"):
+    """`qpos_to_smpl` computed on the device (uhc_qpos_smpl, uhc_amd.sim.qpos_smpl_device): same arguments, the results float64 device tensors --
+    pose_aa (T, 24, 3), trans (T, 3).  The rows are read where they lie when qpos is a device tensor.  SMPL-H, which the host function converts, is not built here."""
+    from ..sim import qpos_smpl_device
+    if smpl_model != "smpl":
+        raise NotImplementedError("qpos_to_smpl_device: only the 24-joint SMPL layout is built on the device (qpos_to_smpl converts SMPL-H on the host)")
+    import torch
+    pose, trans, _ = qpos_smpl_device(torch.as_tensor(qpos), mj_model)
+    return pose.view(-1, 24, 3), trans
+
+
+def smpl_6d_to_qpose_device(full_pose, model, normalize=False):
+    """`smpl_6d_to_qpose` computed on the device (uhc_smpl6d_qpos, uhc_amd.sim.smpl6d_qpos_device): same arguments, the result a float64 device tensor (T, 76)."""
+    from ..sim import smpl6d_qpos_device
+    if normalize:
+        raise NotImplementedError("only the options the copycat path uses are built (SURVEY.md 8f-4)")  # (as smpl_to_qpose refuses it)
+    import torch
+    return smpl6d_qpos_device(torch.as_tensor(full_pose).reshape(-1, 147), [0], model)[0]
+
+
 def smpl_6d_to_qpose(full_pose, model, normalize=False):
     """[trans (3) | 24 x 6D rotations] -> qpos (smpl_mujoco.py:776-780): the 6D blocks are the first two COLUMNS of each rotation matrix
     (process_amass_db.convert_aa_to_orth6d); Gram-Schmidt gives the matrix back, its rotation vector goes through `smpl_to_qpose`."""

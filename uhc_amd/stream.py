@@ -34,13 +34,16 @@ class StreamTracker:
         self.env.reset(self._ids)
         return self.env.obs
 
-    def step(self, next_qpos=None, restart=None, root_quat_record=None):
+    def step(self, next_qpos=None, restart=None, root_quat_record=None, smpl=False):
         """One control step of every env: mean action of the policy on the filtered observation; `next_qpos` (n_env, 76), when given, is appended to the
         streams BEFORE the step (restart (n_env,): non-zero rows start a new stream instead -- the caller resets those envs).  Returns (qpos view
-        (n_env, nq), done view (n_env,))."""
+        (n_env, nq), done view (n_env,)); with smpl=True (qpos, done, pose_aa (n_env, 72), trans (n_env, 3)): the state after the step in the form the
+        targets came in (`VecHumanoidEnv.smpl_pose`: one more launch, no readback; the env's own tensors, written again by the next such step)."""
         with torch.no_grad():
             action = self.policy_net.select_action(self._state(), True).to(torch.float64).contiguous()
         if next_qpos is not None:
             self.env.live_push(self._ids, next_qpos, restart=restart, root_quat_record=root_quat_record)
         self.env.step(action)
+        if smpl:
+            return (self.env.sim.field(S.F_QPOS), self.env.done) + self.env.smpl_pose(("pose_aa", "trans"))
         return self.env.sim.field(S.F_QPOS), self.env.done

@@ -114,6 +114,12 @@ class Config(Base_Config):
         self.eval_surface = g("eval_surface", False)
         if not isinstance(self.eval_surface, bool):
             raise ValueError(f"eval_surface: true or false, got {self.eval_surface!r}")
+        # whether eval_seqs also hands every clip's motion back as SMPL parameters (the first half of the reference env's convert_2_smpl_params): pred_pose_aa /
+        # pred_trans / gt_pose_aa / gt_trans.  With eval_build "device" ONE uhc_qpos_smpl launch reads the record (and one the bank); with "host" qpos_to_smpl.
+        # False (default): eval_seqs returns what it always returned
+        self.eval_smpl = g("eval_smpl", False)
+        if not isinstance(self.eval_smpl, bool):
+            raise ValueError(f"eval_smpl: true or false, got {self.eval_smpl!r}")
         self.ppo_dtype = g("ppo_dtype", "float64")
         # data-parallel gradient exchange: the dtype on the wire.  float32 (default): SURVEY 8e's 32 MB per optimisation epoch; the local
         # gradient means travel scaled by the rank's sample count and are divided by the global count in the parameters' own float64, so the
