@@ -428,8 +428,9 @@ int32_t uhc_env_step(UhcEnv* e, const double* d_action, const int32_t* d_active)
  *                       env outside [0, n_env): the row is ignored; no read or write goes through the index.
  *                       d_restart[r] != 0: the row becomes frame 0 of a NEW stream, with the one-frame-clip record (zero qvel, bangvel); the stream's length
  *                         is 1, its lowest root height the row's, dropped = 0; d_model[r] (outside 0 .. n_models - 1: 0) becomes the env's model.
- *                       otherwise the row is appended at L = the stream's length: L == 0 (no stream) or L == cap: dropped[env] += 1, nothing else is
- *                         written.  Else slot L gets the record of the pair (previous row, row); when L == 1, frame 0's qvel and bangvel are overwritten
+ *                       otherwise the row is appended at L = the stream's length (after the slide, where uhc_env_live_slide is on): L == 0 (no stream) or
+ *                         L == cap: dropped[env] += 1, nothing else is written.  Else slot L gets the record of the pair (previous row, row); when the row is
+ *                         the stream's frame 1 (L == 1 and nothing has slid off), frame 0's qvel and bangvel are overwritten
  *                         with this record's (cat(qvel[0:1], qvel)): the stream's records ARE uhc_expert_frames' of the same rows, bit for bit.
  *                       Offsets come from the env's current model.  cur_t, done, the observation and the simulation state are not touched: after pushing the
  *                       head of a stream the caller resets with uhc_env_reset(ids).
@@ -447,13 +448,34 @@ int32_t uhc_env_step(UhcEnv* e, const double* d_action, const int32_t* d_active)
  *   - with fewer, the newest frame stands in for the missing ones;
  *   - `end` is raised when cur_t >= len - 1 + env_expert_trail_steps -- the stream has run dry -- or at env_episode_len;
  *   - `percent` is cur_t / (len - 1) with the length at that moment;
- *   - observation v3 looks fut_frames skip frames ahead and sees the newest frame for whatever is not there yet. */
+ *   - observation v3 looks fut_frames skip frames ahead and sees the newest frame for whatever is not there yet.
+ *
+ * Endless streams: the window slides (off by default; uhc_env_live_begin switches it off and clears base and moved).
+ * uhc_env_live_slide  on != 0: from now on uhc_env_live_push makes room before it appends, for every listed env whose stream is FULL (len == cap): the S =
+ *                     min(start_ind + cur_t, len - 1) records behind the frame the env reads next are discarded, the others move to the front of the env's
+ *                     slice (one more launch in front of the append, on the batch's stream; no allocation, no host read: still capturable), and len, the
+ *                     env's window length and its internal start index drop by S.  What a slide keeps: every frame the env kernels can still read -- the
+ *                     current one (observation v0), cur_t + 1 and the look-aheads -- and always the newest, so a stream that has run dry keeps holding it.
+ *                     Target, reward, termination, `end`, cur_t and the observations are those of a stream that never slid, bit for bit; a bank of cap =
+ *                     a few times the producer's lead serves a session of any length.  S == 0 on a full stream (the env has not stepped since the last
+ *                     slide): the row is dropped and counted as without sliding.  An env that is not listed, a foreign id and a restart row are not slid.
+ *                     on == 0: pushes stop sliding; the window stays readable where it is, the next push to a full stream is dropped.
+ *                     Refused: not in live mode; obs_v 0 with the phase word (obs_flags & 4), whose cur_t / len would jump at a slide.
+ *                     Under sliding, `percent` is cur_t / (len - 1) of the WINDOW at that moment and is no progress measure; height_lb stays the minimum
+ *                     over the whole stream since the restart; uhc_env_reset WITHOUT a restart row re-seats the env on the window's oldest kept frame
+ *                     (slot 0), not on the stream's first frame, which is gone.  After a restart row, push the head and uhc_env_reset BEFORE the stream
+ *                     fills: until the reset the env's cur_t is the old episode's, and a slide would discard the head's frames behind it.
+ * uhc_env_live_window device pointers d_base, d_moved int32 [n_env]; either may be NULL.  base[env]: frames slid off since the restart -- the global index of
+ *                     the frame in slot i of uhc_env_live_view is base[env] + i, and base + len is the number of frames the stream has accepted.
+ *                     moved[env]: records copied by slides since the restart (what sliding costs).  Both are 0 while sliding was never switched on. */
 int32_t uhc_env_live_begin(UhcEnv* e, int32_t cap, int32_t n_body, const int32_t* h_parent, const int32_t* h_ee_body, const double* d_body_pos,
                            const double* d_body_ipos, int32_t n_models, double dt, const double* d_beta);
 int32_t uhc_env_live_push(UhcEnv* e, const int32_t* d_env_ids, int32_t n, const double* d_qpos, const double* d_root_quat_record,
                           const int32_t* d_restart, const int32_t* d_model);
 int32_t uhc_env_live_view(UhcEnv* e, double** d_frames, int32_t** d_len, int32_t** d_dropped, int32_t* cap);
 int32_t uhc_env_live_end(UhcEnv* e);
+int32_t uhc_env_live_slide(UhcEnv* e, int32_t on);
+int32_t uhc_env_live_window(UhcEnv* e, int32_t** d_base, int32_t** d_moved);
 
 /* ------------------------------------------------------------------ rollout bookkeeping (one control step of the sampling loop)
  * The reference's sample_worker (uhc/khrylib/rl/agents/agent.py:60-100) does, per env step on the host: running_state(state),

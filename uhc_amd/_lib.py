@@ -24,6 +24,7 @@ SYMBOLS = [
     "uhc_env_live_begin", "uhc_env_live_push", "uhc_env_live_view", "uhc_env_live_end",
     "uhc_surface_create", "uhc_surface_free", "uhc_surface_metrics", "uhc_eval_record_pose",
     "uhc_qpos_smpl", "uhc_smpl6d_qpos",
+    "uhc_env_live_slide", "uhc_env_live_window",
 ]
 
 
@@ -116,6 +117,10 @@ def lib():
         L.uhc_qpos_smpl.argtypes = [P, I, C.POINTER(I), I, P, I, P, C.c_int64, I, I, P, P, P, P, P, P, C.POINTER(I)]
         L.uhc_smpl6d_qpos.argtypes = [P, I, C.POINTER(I), P, I, P, C.c_int64, P, P, I, P, P]
         L.uhc_qpos_smpl.restype = L.uhc_smpl6d_qpos.restype = I
+    if hasattr(L, "uhc_env_live_slide"):  # (additive within ABI 11)
+        L.uhc_env_live_slide.argtypes = [P, I]
+        L.uhc_env_live_window.argtypes = [P, C.POINTER(P), C.POINTER(P)]
+        L.uhc_env_live_slide.restype = L.uhc_env_live_window.restype = I
     _lib = L
     return L
 

@@ -685,17 +685,22 @@ def _eval_seq(self, take_key, loader):
 
 
 @torch.no_grad()
-def _track_stream(self, source, n_steps, n_env=None, head=3):
+def _track_stream(self, source, n_steps, n_env=None, head=3, cap=None):
     """The agent's policy (mean action, frozen filter) follows a LIVE source instead of a clip of the bank: `source(t)` returns frame t of every env's
     target motion as a device tensor (n_env, 76) -- hinge qpos rows, what smpl_qpos_device gives -- or None when there is no new frame.  Frames
     0 .. head - 1 are asked for up front (head >= 2; with 3 the first step sees what it would see of a clip), frame t + head before step t
     (uhc_amd.stream.StreamTracker on an env in live mode: VecHumanoidEnv.live_begin / live_push).  Returns (qpos (n_env, n_steps, nq), the step at
-    which each env's episode ended -- n_steps where it did not; the envs are stepped on after that), both on the device."""
+    which each env's episode ended -- n_steps where it did not; the envs are stepped on after that), both on the device.
+    cap=None: the bank holds the whole run, n_steps + head + 1 frames per env.  cap given: the bank holds `cap` frames per env and slides
+    (VecHumanoidEnv.live_begin(cap, slide=True)), so its size no longer grows with n_steps; the trajectory is the same.  cap >= head + 1."""
     from ..stream import StreamTracker
     cfg = self.cfg
     n = int(n_env or cfg.n_env)
     if head < 2:
         raise ValueError("track_stream: head must be at least 2 (a stream needs a pair of frames for its velocities)")
+    if cap is not None and int(cap) < int(head) + 1:
+        raise ValueError(f"track_stream: cap = {cap} is below head + 1 = {int(head) + 1}: the first push after the head would find the window full with an env "
+                         "that has not stepped, and rows would be dropped")
     self._stream_envs = getattr(self, "_stream_envs", {})
     ev = self._stream_envs.get(n)
     if ev is None:
@@ -704,7 +709,10 @@ def _track_stream(self, source, n_steps, n_env=None, head=3):
         ev = self._stream_envs[n] = VecHumanoidEnv(cfg, n_env=n, device=self.env.device.index or 0, mode="test", model=self.env.body_model,
                                                    shape_models=self.env.body_models[1:])
     ev.set_rfc_rate(self.env.rfc_rate)
-    ev.live_begin(int(n_steps) + int(head) + 1)
+    if cap is None:
+        ev.live_begin(int(n_steps) + int(head) + 1)
+    else:
+        ev.live_begin(int(cap), slide=True)
     tracker = StreamTracker(ev, self.policy_net, self.running_state, dtype=self.dtype)
     tracker.begin(torch.stack([torch.as_tensor(source(t)).to(ev.device, torch.float64) for t in range(head)], 1))
     out = torch.zeros((n, int(n_steps), int(ev.model.nq)), dtype=torch.float64, device=ev.device)

@@ -10,8 +10,9 @@
 #include "uhc_expert_math.h"  // XfTree: the kinematic tree uhc_env_live_push hands its kernel
 
 extern "C" hipError_t uhc_launch_live_push(const EnvArgs* E, const XfTree* tree, double dt, int cap, int n_models, double* bank, double* prev_qpos,
-                                           int* live_len, int* dropped, const double* body_pos, const double* body_ipos, const int* env_ids, int n,
-                                           const double* qpos, const double* root_record, const int* restart, const int* model, hipStream_t s);
+                                           int* live_len, int* dropped, int* live_base, int* live_moved, int slide, const double* body_pos,
+                                           const double* body_ipos, const int* env_ids, int n, const double* qpos, const double* root_record,
+                                           const int* restart, const int* model, hipStream_t s);
 extern "C" hipError_t uhc_launch_env_pre(const EnvArgs* E, const int* d_active, hipStream_t s);
 extern "C" hipError_t uhc_launch_env_post(int mode, const EnvArgs* E, const double* d_action, const int* d_active, hipStream_t s);
 extern "C" hipError_t uhc_launch_env_reset_stage(const EnvArgs* E, const int* env_ids, int n, const double* noise, double* out_qpos,
@@ -50,6 +51,9 @@ struct UhcEnv {
     XfTree live_tree = {};
     double *live_bank = nullptr, *live_prev_qpos = nullptr, *live_beta = nullptr, *live_body_pos = nullptr, *live_body_ipos = nullptr;
     int *live_len = nullptr, *live_dropped = nullptr, *live_clip_start = nullptr;
+    // sliding (uhc_env_live_slide): frames slid off / records copied since the restart, per env; live_begin switches it off
+    bool live_slide = false;
+    int *live_base = nullptr, *live_moved = nullptr;
 };
 #define NOT_WHILE_LIVE(e, who) \
     if ((e)->live) return uhc_internal_set_error(who ": the env is in live mode (uhc_env_live_begin): a stream has no window to assign or queue -- push a restart row and uhc_env_reset, or uhc_env_live_end first")
@@ -296,12 +300,14 @@ extern "C" int32_t uhc_env_live_begin(UhcEnv* e, int32_t cap, int32_t n_body, co
         e->live_bank = (double*)q, e->live_alloc_cap = cap;
     }
     if (!e->live_len && (dalloc(e, N * XF_NQ, &e->live_prev_qpos) || dalloc(e, N, &e->live_len) || dalloc(e, N, &e->live_dropped) ||
-                         dalloc(e, N, &e->live_clip_start) || dalloc(e, N * 17, &e->live_beta) ||
+                         dalloc(e, N, &e->live_clip_start) || dalloc(e, N * 17, &e->live_beta) || dalloc(e, N, &e->live_base) || dalloc(e, N, &e->live_moved) ||
                          dalloc(e, (size_t)n_models * XF_NBODY * 3, &e->live_body_pos) || dalloc(e, (size_t)n_models * XF_NBODY * 3, &e->live_body_ipos)))
         return 1;
     hipStream_t s = stream_of(e);
     HIP_OK(hipMemsetAsync(e->live_len, 0, N * sizeof(int), s));  // every stream is cleared: an append without a restart is dropped
     HIP_OK(hipMemsetAsync(e->live_dropped, 0, N * sizeof(int), s));
+    HIP_OK(hipMemsetAsync(e->live_base, 0, N * sizeof(int), s));
+    HIP_OK(hipMemsetAsync(e->live_moved, 0, N * sizeof(int), s));
     HIP_OK(hipMemsetAsync(e->live_prev_qpos, 0, N * XF_NQ * sizeof(double), s));
     // every slot is zeroed and every env points at a window of ONE frame inside its own stream: a reset or a step before the first push reads zeros,
     // never a frame outside the bank (the env kernels clamp to e_len - 1, and e_start of an earlier bank means nothing here)
@@ -317,7 +323,7 @@ extern "C" int32_t uhc_env_live_begin(UhcEnv* e, int32_t cap, int32_t n_body, co
     HIP_OK(hipMemcpy(e->live_body_pos, d_body_pos, (size_t)n_models * XF_NBODY * 3 * sizeof(double), hipMemcpyDeviceToDevice));
     HIP_OK(hipMemcpy(e->live_body_ipos, d_body_ipos, (size_t)n_models * XF_NBODY * 3 * sizeof(double), hipMemcpyDeviceToDevice));
     HIP_OK(hipStreamSynchronize(s));
-    e->live = true, e->live_cap = cap, e->live_models = n_models, e->live_dt = dt, e->live_tree = tree;
+    e->live = true, e->live_slide = false, e->live_cap = cap, e->live_models = n_models, e->live_dt = dt, e->live_tree = tree;
     e->E.bank = e->live_bank, e->E.clip_start = e->live_clip_start, e->E.clip_beta = e->live_beta;
     e->E.obj_pose = nullptr, e->E.clip_model = nullptr, e->E.env_model = em;
     e->n_clips = (int)N, e->n_frames = (int64_t)N * cap;
@@ -332,7 +338,23 @@ extern "C" int32_t uhc_env_live_push(UhcEnv* e, const int32_t* d_env_ids, int32_
     if (!e) return uhc_internal_set_error("uhc_env_live_push: the env e is NULL");
     if (!e->live) return uhc_internal_set_error("uhc_env_live_push: the env is not in live mode (uhc_env_live_begin)");
     HIP_OK(uhc_launch_live_push(&e->E, &e->live_tree, e->live_dt, e->live_cap, e->live_models, e->live_bank, e->live_prev_qpos, e->live_len, e->live_dropped,
-                                e->live_body_pos, e->live_body_ipos, d_env_ids, n, d_qpos, d_root_quat_record, d_restart, d_model, stream_of(e)));
+                                e->live_base, e->live_moved, e->live_slide ? 1 : 0, e->live_body_pos, e->live_body_ipos, d_env_ids, n, d_qpos, d_root_quat_record,
+                                d_restart, d_model, stream_of(e)));
+    return 0;
+}
+extern "C" int32_t uhc_env_live_slide(UhcEnv* e, int32_t on) {
+    if (!e) return uhc_internal_set_error("uhc_env_live_slide: the env e is NULL");
+    if (!e->live) return uhc_internal_set_error("uhc_env_live_slide: the env is not in live mode (uhc_env_live_begin)");
+    if (on && e->E.obs_v == 0 && (e->E.obs_flags & 4))
+        return uhc_internal_set_error("uhc_env_live_slide: the env's observation carries the phase word (obs_v 0 with obs_flags & 4): cur_t / len would jump at a slide");
+    e->live_slide = on != 0;
+    return 0;
+}
+extern "C" int32_t uhc_env_live_window(UhcEnv* e, int32_t** d_base, int32_t** d_moved) {
+    if (!e) return uhc_internal_set_error("uhc_env_live_window: the env e is NULL");
+    if (!e->live) return uhc_internal_set_error("uhc_env_live_window: the env is not in live mode (uhc_env_live_begin)");
+    if (d_base) *d_base = e->live_base;
+    if (d_moved) *d_moved = e->live_moved;
     return 0;
 }
 extern "C" int32_t uhc_env_live_view(UhcEnv* e, double** d_frames, int32_t** d_len, int32_t** d_dropped, int32_t* cap) {

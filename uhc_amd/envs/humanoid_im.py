@@ -273,16 +273,24 @@ class VecHumanoidEnv:
         self.env.assign(torch.as_tensor(env_ids, dtype=torch.int32), cid, fs, fl)
 
     # ---- live targets: the envs imitate frames that arrive while they run (a kinematic policy, a pose estimator, teleoperation) ----------
-    def live_begin(self, cap, beta=None):
+    def live_begin(self, cap, beta=None, slide=False):
         """Every env gets a stream of up to `cap` frames in a bank the library owns (n_env x cap x 4 672 B) in place of the clip bank; beta
         (n_env, 17) or None: what has_shape observations append.  Then: live_push(ids, rows, restart=ones) frame 0, live_push the frames that
-        are there, reset(ids), and one live_push per control step.  assign / set_next / auto_reset are refused until live_end / set_clip_bank."""
+        are there, reset(ids), and one live_push per control step.  assign / set_next / auto_reset are refused until live_end / set_clip_bank.
+        slide=False: a stream holds `cap` frames and drops what comes after them.  slide=True: the stream is endless -- a push to a full stream first
+        discards the frames behind the one the env reads next and moves the others to the front (uhc_env_live_slide), so `cap` need only be a few
+        times the producer's lead (at least head + 1) whatever the session's length; the envs are driven exactly as without sliding.  Then
+          - UHC_E_PERCENT (`percent`) is cur_t / (len - 1) of the WINDOW and is not a progress measure;
+          - reset(ids) without a restart row re-seats the env on the window's oldest kept frame, not on the stream's first one;
+          - after a restart row, push the head and reset before the stream fills (until the reset, cur_t is the old episode's)."""
         if self.num_obj:
             raise NotImplementedError("live targets: object poses per live frame are not built")
         for i, m in enumerate(self.body_models):
             if i not in self._humanoids:
                 self._humanoids[i] = Humanoid(model=m)
         self.env.live_begin(cap, [self._humanoids[i] for i in range(len(self.body_models))], beta=beta, dt=1 / 30)
+        if slide:
+            self.env.live_slide(True)
         self.clip_keys, self._clip_index, self._clip_len = [], {}, None
 
     def live_push(self, env_ids, qpos, restart=None, root_quat_record=None, model=None):
@@ -348,6 +356,11 @@ class VecHumanoidEnv:
 
     def live_view(self):
         return self.env.live_view()
+
+    def live_window(self):
+        """(base (n_env,), moved (n_env,)) int32 views: frames slid off since the restart (slot i of live_view()[0] is global frame base + i; base + len
+        frames were accepted) and records copied by slides.  Zeros without slide=True."""
+        return self.env.live_window()
 
     def live_end(self):
         self.env.live_end()

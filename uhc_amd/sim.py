@@ -655,6 +655,23 @@ class EnvBatch:
                           torch.as_tensor(_DevView(pd.value, (self.n_env,), "<i4", self), device=self.device))
         return self._live
 
+    def live_slide(self, on: bool = True):
+        """Endless streams (uhc_env_live_slide; `live_begin` switches it off): from now on `live_push` makes room before it appends -- where a listed env's
+        stream is full, the records behind the frame the env reads next are discarded and the others move to the front of its slice, on the device, in the
+        same call.  The env is driven exactly as by a stream that never slid; `E_PERCENT` is then cur_t / (len - 1) of the window, not a progress measure.
+        Refused outside live mode and for observation v0 with the phase word."""
+        check(self.L.uhc_env_live_slide(self._e, 1 if on else 0))
+
+    def live_window(self):
+        """(base (n_env,), moved (n_env,)): zero-copy int32 views.  base: frames slid off since the restart -- slot i of `live_view()[0]` holds global frame
+        base + i, and base + len frames were accepted --; moved: records copied by slides since the restart."""
+        if getattr(self, "_live_win", None) is None or self._live_win[0] != self.generation:
+            pb, pm = C.c_void_p(), C.c_void_p()
+            check(self.L.uhc_env_live_window(self._e, C.byref(pb), C.byref(pm)))
+            self._live_win = (self.generation, torch.as_tensor(_DevView(pb.value, (self.n_env,), "<i4", self), device=self.device),
+                              torch.as_tensor(_DevView(pm.value, (self.n_env,), "<i4", self), device=self.device))
+        return self._live_win[1:]
+
     def live_end(self):
         """Leave live mode: the env has no bank until the next `set_bank` / `live_begin` (the live memory stays the env's)."""
         self.generation += 1

@@ -11,7 +11,9 @@ from . import sim as S
 
 class StreamTracker:
     """env: a `VecHumanoidEnv` in live mode (`env.live_begin(cap)`); policy_net: a policy with `select_action(state, mean_action)`; running_state: the
-    policy's observation filter (ZFilter) or None -- applied with update=False, the statistics are those the policy was trained with."""
+    policy's observation filter (ZFilter) or None -- applied with update=False, the statistics are those the policy was trained with.
+    A session of any length: `env.live_begin(cap, slide=True)` with cap a few times the head (at least head + 1) -- the window slides under the envs as
+    `step` pushes, nothing else changes here; without slide, cap bounds the session and later rows are dropped."""
 
     def __init__(self, env, policy_net, running_state=None, dtype=torch.float64):
         self.env, self.policy_net, self.running_state, self.dtype = env, policy_net, running_state, dtype
@@ -24,7 +26,8 @@ class StreamTracker:
 
     def begin(self, head, root_quat_record=None):
         """head (n_env, k >= 2, 76): the first k target rows of every env's stream (device or host).  Frame 0 restarts the streams, the others are
-        appended, the envs are reset onto frame 0; returns the observation view.  root_quat_record (n_env, k, 4): the ball-joint humanoid's."""
+        appended, the envs are reset onto frame 0; returns the observation view.  root_quat_record (n_env, k, 4): the ball-joint humanoid's.
+        (On a sliding env k <= cap - 1, so that the first push after the reset finds room.)"""
         head = torch.as_tensor(head).to(self.env.device, torch.float64)
         if head.ndim != 3 or head.shape[0] != self.env.n_env or head.shape[1] < 2 or head.shape[2] != 76:
             raise ValueError(f"StreamTracker.begin: head must be ({self.env.n_env}, k >= 2, 76), got {tuple(head.shape)}")
