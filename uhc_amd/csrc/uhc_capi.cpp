@@ -185,7 +185,7 @@ static int upload_plan(UhcBatch* b, const BatchPlan& P, const UhcModelDesc& d, c
     TRY(upload(b, ivec(d.dof_bodyid, nv), &T.dof_bodyid)); TRY(upload(b, ivec(d.dof_jntid, nv), &T.dof_jntid));
     TRY(upload(b, ivec(d.dof_parentid, nv), &T.dof_parentid)); TRY(upload(b, ivec(d.dof_madr, nv + 1), &T.dof_madr));
     TRY(upload(b, P.dof_depth, &T.dof_depth)); TRY(upload(b, P.dof_ndesc, &T.dof_ndesc));
-    TRY(upload(b, P.dof_anc, &T.dof_anc)); TRY(upload(b, P.ncommon, &T.dof_ncommon)); TRY(upload(b, P.m_row, &T.m_row)); TRY(upload(b, P.m_col, &T.m_col)); TRY(upload(b, P.m_ij, &T.m_ij));
+    TRY(upload(b, P.dof_anc, &T.dof_anc)); TRY(upload(b, P.chainmask, &T.dof_chainmask)); TRY(upload(b, P.m_row, &T.m_row)); TRY(upload(b, P.m_col, &T.m_col)); TRY(upload(b, P.m_ij, &T.m_ij));
     TRY(upload(b, ivec(d.geom_type, ng), &T.geom_type)); TRY(upload(b, ivec(d.geom_bodyid, ng), &T.geom_bodyid));
     TRY(upload(b, ivec(d.geom_condim, ng), &T.geom_condim)); TRY(upload(b, ivec(d.geom_vertadr, ng), &T.geom_vertadr));
     TRY(upload(b, ivec(d.geom_vertnum, ng), &T.geom_vertnum));

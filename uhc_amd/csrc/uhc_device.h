@@ -84,7 +84,7 @@ struct DevTopo {
     const short* dof_anc;  // [nv][maxdepth+1]: ancestor of dof i at depth q (q <= depth(i)), anc[i][depth(i)] = i
     const short *m_row, *m_col;  // [nM] sparse-M entry -> (i, j)
     const unsigned short* m_ij;  // [nM (+pad)] the same, packed i << 8 | j (nv <= 128)
-    const unsigned char* dof_ncommon;  // [nv][nv] number of common chain entries of two dofs (depth of LCA + 1, 0 if none)
+    const unsigned long long* dof_chainmask;  // [nv][2] bit d of the 128: dof d is on the chain of dof i (its position = the set bits below it; nv <= 128)
     const int *geom_type, *geom_bodyid, *geom_condim, *geom_vertadr, *geom_vertnum;
     const int *pair_g1, *pair_g2;  // statically filtered candidate geom pairs (g1 = plane, g2 = mesh)
     const int *cpair_g1, *cpair_g2;  // statically filtered convex-convex candidate pairs (mesh, mesh), g1 < g2, in (g1, g2) order
@@ -126,8 +126,8 @@ struct DevLds {
     int rowW;   // general / large tiers: the warm-start forces, kept for the sweeps fallback of the working-set solve
     int rowY;   // general / large tiers: ints [maxefc] offset of every row's packed Yhat entries inside Y
     int dense;  // [ndense][nvp] dense Yhat rows of the constraints that touch two moving bodies (self-collision, objects)
-    int dcol;   // [ndense][64] column of the Delassus matrix of every dense row (A is symmetric: the row's lane reads it back); in the general /
-                // large layouts it shares the contacts' storage, which nothing reads once the rows are built
+    int dcol;   // [ndense][64] UNUSED since the Delassus build runs on the matrix unit (it held the dense rows' columns of A, written by a pre-pass of k_pgs_fast);
+                // the offset stays because the planner's recorded layouts name it.  It shares the contacts' storage except under UHC_FAST_DCOL_OWN=1
     int dsc;    // general kernel: [ndense][4] J.qvel, J.qacc_smooth, J.qacc_warmstart, |Yhat|^2 of every dense row
     int H;      // tier 4: the Hessian of the primal problem, packed lower triangle column by column (nv (nv + 1) / 2 doubles)
     int total;  // doubles

@@ -214,6 +214,19 @@ __device__ __forceinline__ void static_for(F&& f) {
 // finished Delassus row while it is being built, and the mass matrix between substeps (MPark).
 __device__ __forceinline__ void agpr_put(int& a, int v) { asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(v)); }
 __device__ __forceinline__ int agpr_get(int a) { int v; asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a)); return v; }
+// the Delassus build's tiles (k_pgs_fast): the accumulator of one v_mfma_f64_16x16x4_f64, and the two lane exchanges of its way back to lane = row
+#include "uhc_delassus_tiles.h"
+typedef double dt_acc __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void dt_swap32(double& x, double& y) {  // lanes 32 .. 63 of x <-> lanes 0 .. 31 of y (dt_swap32_lane)
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
+    x = __hiloint2double((int)hi[0], (int)lo[0]); y = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+__device__ __forceinline__ void dt_swap16(double& x, double& y) {  // the odd 16-lane groups of x <-> the even ones of y (dt_swap16_lane)
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
+    x = __hiloint2double((int)hi[0], (int)lo[0]); y = __hiloint2double((int)hi[1], (int)lo[1]);
+}
 #define UHC_MREG 24
 // the joint-space inertia of the last forward pass (entries LANE + 64 m), parked in AGPRs: the PD solve of the next substep
 // reads it back (the fast layout factorises M in place, so LDS does not keep it)
@@ -1736,7 +1749,7 @@ __device__ __forceinline__ int k_rows_fast(const KernelArgs& A, const double* mb
             });
         }
     });
-    if (LANE < 8) S[L.Y + total + LANE] = 0.0;  // the A build reads rows in chunks of 8: finite slack after the last row
+    if (LANE < 8) S[L.Y + total + LANE] = 0.0;  // the A build's gather may stand one entry past a row's end (and not use what it reads): finite slack after the last row
     double* Yst = S + L.Y + row.yoff;
     static_for<0, UHC_YM / 4>([&](auto gc) __attribute__((always_inline)) {
         constexpr int g4 = decltype(gc)::value;
@@ -1897,7 +1910,7 @@ __device__ __forceinline__ int as_solve(const int (&Alo)[UHC_WAVE], const int (&
 // LT: the tier whose LDS layout the rows live in (the general / large tiers solve working sets of <= 64 of their rows with the same code).
 // SL[0 .. nslot): lane that holds the dense row of slot k (an entry outside [0, nefc) = that row is not part of this solve).
 template <int LT, bool DENSE>
-__device__ __forceinline__ int k_pgs_fast(const KernelArgs& A, const double* mb, double* S, int nefc, FastRow& row, const double (&Y)[UHC_YM], const LaneConst& LC,
+__device__ __forceinline__ int k_pgs_fast(const KernelArgs& A, const double* mb, double* S, int nefc, FastRow& row, const LaneConst& LC,
                                           const int* SL, int nslot PROF_ARGS) {
     const DevTopo& T = A.t;
     const DevLds& L = lds_of<LT>(A);
@@ -1907,109 +1920,97 @@ __device__ __forceinline__ int k_pgs_fast(const KernelArgs& A, const double* mb,
         for (int k = 0; k < nslot; k++) ntwo += (unsigned)SL[k] < (unsigned)nefc;
         ntwo = __builtin_amdgcn_readfirstlane(ntwo);
     }
-    // ---- Delassus columns of the dense rows: A[l][c] = Yhat_l . Yhat_c for every lane l, kept in LDS (dcol[slot][lane]): lane l reads its
-    //      entry when column c comes up below, and -- A being symmetric -- the lane that owns dense row c reads its whole ROW from there.
-    if (DENSE && ntwo > 0) {
-        unsigned int cdq[UHC_YM];
-        const unsigned int* chain = T.chain + (size_t)(row.last >= 0 ? row.last : 0) * UHC_YM;
-        static_for<0, UHC_YM>([&](auto qc) __attribute__((always_inline)) { constexpr int q = decltype(qc)::value; cdq[q] = chain[q] & 0xffffu; });
-        for (int k = 0; k < nslot; k++) {
-            if ((unsigned)__builtin_amdgcn_readfirstlane(SL[k]) >= (unsigned)nefc) continue;
-            const double* Dk = S + L.dense + k * A.nvp;
-            double acc = 0.0;
-            static_for<0, UHC_YM>([&](auto qc) __attribute__((always_inline)) {
-                constexpr int q = decltype(qc)::value;
-                acc = fma(Y[q], Dk[cdq[q]], acc);  // Y is zero past the row's own chain (and for dense rows)
-            });
-            S[L.dcol + k * UHC_WAVE + LANE] = valid ? acc : 0.0;  // (dense lanes: 0 for now)
-        }
-        wsync();
-        // dense x dense entries: one wave reduction per pair of slots (lane = dof), written to both lanes' columns
-        for (int k = 0; k < nslot; k++) {
-            const int lk = __builtin_amdgcn_readfirstlane(SL[k]);
-            if ((unsigned)lk >= (unsigned)nefc) continue;
-            const double* Dk = S + L.dense + k * A.nvp;
-            const double dk0 = LC.v0 ? Dk[LANE] : 0.0, dk1 = LC.v1 ? Dk[LANE + UHC_WAVE] : 0.0;
-            for (int m = 0; m <= k; m++) {
-                const int lm = __builtin_amdgcn_readfirstlane(SL[m]);
-                if ((unsigned)lm >= (unsigned)nefc) continue;
-                const double* Dm = S + L.dense + m * A.nvp;
-                const double v = wave_sum(dk0 * (LC.v0 ? Dm[LANE] : 0.0) + dk1 * (LC.v1 ? Dm[LANE + UHC_WAVE] : 0.0));
-                if (LANE == 0) { S[L.dcol + k * UHC_WAVE + lm] = v; S[L.dcol + m * UHC_WAVE + lk] = v; }
-            }
-        }
-        wsync();
-    }
-    // ---- A[r][s] = sum over the common part of the two dof chains, entirely in registers: row s is broadcast from lane
-    //      the packed LDS rows (same address in all lanes), the own row is pre-masked to the common chain prefix.  Rows of one body are
-    //      adjacent and share that prefix length, so the masked copy is rebuilt only when the body changes.
-    unsigned int ncp[UHC_WAVE / 4];  // common-prefix length of this lane's chain with every row's chain, 4 per register
-    {
-        int nraw[UHC_WAVE];
-        static_for<0, UHC_WAVE>([&](auto sc) __attribute__((always_inline)) {
-            constexpr int s = decltype(sc)::value;
-            nraw[s] = 0;
-            if (s < nefc) {
-                const int ls = __builtin_amdgcn_readlane(row.last, s);
-                nraw[s] = (valid && row.last >= 0 && ls >= 0) ? (int)A.t.dof_ncommon[row.last * T.nv + ls] : 0;
-            }
-        });
-        static_for<0, UHC_WAVE / 4>([&](auto jc) __attribute__((always_inline)) {
-            constexpr int j = decltype(jc)::value;
-            ncp[j] = (unsigned)nraw[4 * j] | ((unsigned)nraw[4 * j + 1] << 8) | ((unsigned)nraw[4 * j + 2] << 16) | ((unsigned)nraw[4 * j + 3] << 24);
-        });
-    }
-    double Ym[UHC_YM];
+    // ---- A = Yhat Yhat^T on the matrix unit, in 16 x 16 tiles of v_mfma_f64_16x16x4_f64 (index maps: uhc_delassus_tiles.h).  For a row block J and a panel
+    //      of four dofs, lane l gathers Yhat[16 J + (l & 15)][4 p + (l >> 4)] from LDS -- a packed row through the bit mask of its chain (position = chain dofs
+    //      below the dof), a dense row directly (the chain of all dofs); rows >= nefc, dofs off the chain and dofs >= nv supply 0.0.  The one value is the A
+    //      operand of the tiles (J, .) and the B operand of the tiles (., J), so dense x packed and dense x dense entries come out of the same tiles as the rest.
+    //      Column block after column block: the tiles (I, 0 .. nblk) accumulate over all panels, the next panel's gathers issued ahead of the instructions
+    //      that use them; then a 4 x 4 transposition among the lanes {g, g + 16, g + 32, g + 48} (two rounds of v_permlane32_swap / v_permlane16_swap per
+    //      register) brings lane r the columns 16 I .. 16 I + 15 of ITS row, which go to the AGPR-parked Alo / Ahi.  Blocks >= nblk are skipped uniformly.
     int Alo[UHC_WAVE], Ahi[UHC_WAVE];  // AGPR-parked A[r][s]
     double diag = 1.0;
-    int prev = -1;
-    static_for<0, UHC_YM>([&](auto qc) __attribute__((always_inline)) { Ym[decltype(qc)::value] = 0.0; });
-    auto build_A = [&](auto dense_c) __attribute__((always_inline)) {
-    constexpr bool DCOL = decltype(dense_c)::value;  // some row of this env is dense
-    static_for<0, UHC_WAVE>([&](auto sc) __attribute__((always_inline)) {
-        constexpr int s = decltype(sc)::value;
-        double acc = 0.0;
-        if (s < nefc) {
-            const int ls = __builtin_amdgcn_readlane(row.last, s);
-            const int lens = __builtin_amdgcn_readlane(row.len, s);
-            const int two_s = DCOL ? __builtin_amdgcn_readlane(row.two, s) : -1;
-            if (DCOL && two_s >= 0) acc = S[L.dcol + two_s * UHC_WAVE + LANE];
-            else {
-            const double* Ys = S + L.Y + __builtin_amdgcn_readlane(row.yoff, s);  // row s in LDS: one broadcast read per entry
-            if (ls != prev) {
-                prev = ls;
-                const int nc = (ncp[s / 4] >> (8 * (s % 4))) & 0xff;
-                static_for<0, UHC_YM>([&](auto qc) __attribute__((always_inline)) {
-                    constexpr int q = decltype(qc)::value;
-                    Ym[q] = q < nc ? Y[q] : 0.0;
+    {
+        const int nblk = __builtin_amdgcn_readfirstlane(dt_row_blocks(nefc));
+        const int npan = dt_panels(T.nv);
+        const int kq = dt_ab_k(LANE);
+        int gbase[UHC_DT_BLOCKS];                                   // LDS offset of the operand row's first entry
+        unsigned long long gm0[UHC_DT_BLOCKS], gm1[UHC_DT_BLOCKS];  // its dofs (0: the row supplies nothing)
+        static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int J = decltype(jc)::value;
+            gbase[J] = L.Y; gm0[J] = 0ull; gm1[J] = 0ull;
+            if (J < nblk) {
+                const int src = dt_gather_row(J, LANE);
+                const int s_last = __builtin_amdgcn_ds_bpermute(src << 2, row.last);
+                const int s_yoff = __builtin_amdgcn_ds_bpermute(src << 2, row.yoff);
+                const int s_two = DENSE ? __builtin_amdgcn_ds_bpermute(src << 2, row.two) : -1;
+                if (src < nefc) {
+                    if (s_two >= 0) { gbase[J] = L.dense + s_two * A.nvp; gm0[J] = dt_all_dofs(T.nv, 0); gm1[J] = dt_all_dofs(T.nv, 1); }
+                    else if (s_last >= 0) { gbase[J] = L.Y + s_yoff; gm0[J] = T.dof_chainmask[2 * s_last]; gm1[J] = T.dof_chainmask[2 * s_last + 1]; }
+                }
+            }
+        });
+        static_for<0, UHC_DT_BLOCKS>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int I = decltype(ic)::value;
+            double w[UHC_DT_TILE];  // this lane's row, columns 16 I ..
+            static_for<0, UHC_DT_TILE>([&](auto mc) __attribute__((always_inline)) { w[decltype(mc)::value] = 0.0; });
+            if (I < nblk) {
+                dt_acc acc[UHC_DT_BLOCKS];
+                static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) { acc[decltype(jc)::value] = dt_acc{0.0, 0.0, 0.0, 0.0}; });
+                for (int h = 0; h < 2; h++) {  // dofs 0 .. 63, 64 .. 127: one word of the masks each
+                    const int p0 = 16 * h, p1 = min(npan, 16 * h + 16);
+                    if (p0 >= p1) break;
+                    // walking state per row block: the mask from this lane's dof on, the LDS offset of the entry it stands at
+                    unsigned long long rmk[UHC_DT_BLOCKS];
+                    int at[UHC_DT_BLOCKS];
+                    static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) {
+                        constexpr int J = decltype(jc)::value;
+                        const unsigned long long wd = h ? gm1[J] : gm0[J];
+                        at[J] = gbase[J] + __popcll(wd & ((1ull << kq) - 1ull)) + (h ? __popcll(gm0[J]) : 0);
+                        rmk[J] = wd >> kq;
+                    });
+                    // (the gather runs one panel ahead, so it may stand ONE entry past its row's end -- past the last panel, and wherever the lane's dof is not
+                    //  on the chain: the next row, the fast layout's slack, or the first word behind the region, all inside the LDS allocation.  What it reads
+                    //  there is SELECTED away by the mask bit, never multiplied, so no value of that word -- a NaN of an earlier workgroup -- reaches A)
+                    auto gather = [&](double (&v)[UHC_DT_BLOCKS]) __attribute__((always_inline)) {
+                        static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) {
+                            constexpr int J = decltype(jc)::value;
+                            v[J] = 0.0;
+                            if (J < nblk) {
+                                const double x = S[at[J]];
+                                v[J] = ((unsigned)rmk[J] & 1u) ? x : 0.0;
+                                at[J] += __popc((unsigned)rmk[J] & 15u);
+                                rmk[J] >>= UHC_DT_PANEL;
+                            }
+                        });
+                    };
+                    double v[UHC_DT_BLOCKS];
+                    gather(v);
+                    for (int p = p0; p < p1; p++) {
+                        double vn[UHC_DT_BLOCKS];
+                        gather(vn);
+                        static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) {
+                            constexpr int J = decltype(jc)::value;
+                            if (J < nblk) acc[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[I], v[J], acc[J], 0, 0, 0);
+                        });
+                        static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) { v[decltype(jc)::value] = vn[decltype(jc)::value]; });
+                    }
+                }
+                static_for<0, 4>([&](auto rc) __attribute__((always_inline)) {
+                    constexpr int i = decltype(rc)::value;
+                    double t0 = acc[0][i], t1 = acc[1][i], t2 = acc[2][i], t3 = acc[3][i];
+                    dt_swap32(t0, t2); dt_swap32(t1, t3); dt_swap16(t0, t1); dt_swap16(t2, t3);
+                    w[4 * i + 0] = t0; w[4 * i + 1] = t1; w[4 * i + 2] = t2; w[4 * i + 3] = t3;  // columns dt_out_col(I, i, 0 .. 3)
                 });
             }
-            // chunks of 8 chain positions, skipped uniformly beyond row s's length; inside a chunk no tests are needed:
-            // Ym is zero past the common prefix (<= lens) and every row's registers are zero past its own length
-            // (all loads of a row up front in two halves of 16 with two accumulators: A-build -8 %, but the rest of the kernel +1.5 %
-            //  from the changed register allocation: not kept)
-            static_for<0, UHC_YM / 8>([&](auto cc) __attribute__((always_inline)) {
-                constexpr int c = decltype(cc)::value;
-                if (8 * c < lens) {
-                    double y8[8];
-                    static_for<0, 8>([&](auto qc) __attribute__((always_inline)) { constexpr int j = decltype(qc)::value; y8[j] = Ys[8 * c + j]; });
-                    static_for<0, 8>([&](auto qc) __attribute__((always_inline)) {
-                        constexpr int j = decltype(qc)::value;
-                        acc = fma(Ym[8 * c + j], y8[j], acc);
-                    });
-                }
+            static_for<0, UHC_DT_TILE>([&](auto mc) __attribute__((always_inline)) {
+                constexpr int m = decltype(mc)::value, s = UHC_DT_TILE * I + m;
+                double a = w[m];
+                if (s == LANE && valid) { a += row.R; diag = a; }
+                agpr_put(Alo[s], __double2loint(a));
+                agpr_put(Ahi[s], __double2hiint(a));
             });
-            if (DCOL && row.two >= 0) acc = S[L.dcol + row.two * UHC_WAVE + s];  // the dense row's own lane: its row of A by symmetry
-            }
-            if (DCOL && !valid) acc = 0.0;
-            if (s == LANE) { acc += row.R; diag = acc; }
-        }
-        agpr_put(Alo[s], __double2loint(acc));
-        agpr_put(Ahi[s], __double2hiint(acc));
-    });
-    };
-    if (DENSE && ntwo > 0) build_A(std::true_type{}); else build_A(std::false_type{});
-    if (!valid) diag = 1.0;
+        });
+    }
     PROF(10)
     const bool any_fric = wave_or(row.type == ROW_FRICTION ? 1 : 0) != 0;
     int iters = -1;
@@ -2375,11 +2376,6 @@ __device__ __forceinline__ int k_as_general(const KernelArgs& A, const double* m
             row.yoff = valid ? RY[r] : 0;
             row.R = valid ? S[L.rowR + r] : 1.0; row.b = valid ? S[L.rowB + r] : 0.0; row.f = 0.0; row.floss = 0.0; row.diag = 1.0;
             if (two) SLg[row.two] = LANE;
-            double Y[UHC_YM];
-            static_for<0, UHC_YM>([&](auto qc) __attribute__((always_inline)) {
-                constexpr int q = decltype(qc)::value;
-                Y[q] = q < row.len ? S[L.Y + row.yoff + q] : 0.0;
-            });
             wsync();
             // ---- windows: the island's force-carrying rows outside C keep their force; zfix = sum of f Yhat over them, b_C += Yhat_C . zfix
             bool fx[NRL];
@@ -2433,7 +2429,7 @@ __device__ __forceinline__ int k_as_general(const KernelArgs& A, const double* m
                 }
             }
             PROF(30)
-            const int it = k_pgs_fast<TIER, DENSE>(A, mb, S, nC, row, Y, LC, SLg, nslot PROF_PASS);  // exact on C (or its sweeps to tolerance); z = sum_C f Yhat
+            const int it = k_pgs_fast<TIER, DENSE>(A, mb, S, nC, row, LC, SLg, nslot PROF_PASS);  // exact on C (or its sweeps to tolerance); z = sum_C f Yhat
             if (it < 0) return UHC_WS_PIVOT;  // pivot breakdown / no convergence of the pivoting on this working set
             iters += it > 0 ? it : 1;
             if (block) {  // z of the whole island
@@ -2559,7 +2555,7 @@ __device__ __forceinline__ FwdOut k_forward(const KernelArgs& A, const double* m
             if (st == UHC_ST_HANDON) return out;
             PROF(9)
             const int* NI = (const int*)(S + L.ncon_nefc);
-            out.iters = k_pgs_fast<1, DENSE>(A, mb, S, out.nefc, row, Yreg, LC, NI + 4, DENSE ? NI[2] : 0 PROF_PASS);
+            out.iters = k_pgs_fast<1, DENSE>(A, mb, S, out.nefc, row, LC, NI + 4, DENSE ? NI[2] : 0 PROF_PASS);
             PROF(12)
         } else {
             double* Yb = y_store<TIER>(A, S, env);

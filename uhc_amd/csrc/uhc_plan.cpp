@@ -1,6 +1,7 @@
 // uhc_plan.cpp -- batch planning: everything uhc_batch_create decides from the model description, the controller and the UHC_* knobs before it
 // allocates anything.  No hip* call in this file; every refusal that does not need the device happens here.
 #include "uhc_plan.h"
+#include "uhc_delassus_tiles.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -164,6 +165,7 @@ static void tree_tables(const UhcModelDesc& d, BatchPlan& P) {
     }
     P.m_ij.assign(T.nM + 4, 0);
     for (int e = 0; e < T.nM; e++) P.m_ij[e] = (unsigned short)((P.m_row[e] << 8) | P.m_col[e]);
+    // (host only since the Delassus build reads the chains as masks, below: kept for the plan recording, which hashes it; to retire with the recording)
     P.ncommon.assign((size_t)nv * nv, 0);
     for (int i = 0; i < nv; i++)
         for (int j = 0; j < nv; j++) {
@@ -172,6 +174,9 @@ static void tree_tables(const UhcModelDesc& d, BatchPlan& P) {
             while (q <= lim && P.dof_anc[(size_t)i * YS + q] == P.dof_anc[(size_t)j * YS + q]) q++;
             P.ncommon[(size_t)i * nv + j] = (unsigned char)q;
         }
+    // the chains as bit masks: the Delassus build finds a dof's position on a chain by counting the chain's dofs below it (uhc_delassus_tiles.h)
+    P.chainmask.assign((size_t)nv * 2, 0ull);
+    for (int i = 0; i < nv; i++) dt_chain_mask(d.dof_parentid, i, &P.chainmask[(size_t)i * 2], &P.chainmask[(size_t)i * 2 + 1]);
     P.dof_rootid.assign(nv, 0);
     for (int i = 0; i < nv; i++) P.dof_rootid[i] = P.body_rootid[d.dof_bodyid[i]];
 }
@@ -360,6 +365,8 @@ static void fast_layout(Carver& cv, const UhcModelDesc& d, int n_env, const Batc
     // the dense rows' Delassus columns are written by the contact solve, when nothing reads the contacts any more (the rows are built):
     // they take the contacts' storage when they fit it (6 slots x 64 lanes = 16 contacts x 24 doubles), as in the larger tiers
     const bool dcol_alias = A.cf.ndense * UHC_WAVE <= fast_maxcon * UHC_CON_STRIDE && !knobs.fast_dcol_own;
+    // (no kernel writes or reads dcol any more -- the dense rows' entries of A come out of the same tiles as the rest, uhc_delassus_tiles.h -- so UHC_FAST_DCOL_OWN=1 only
+    //  spends LDS; offset and knob stay because the recorded layouts of tests/batch_plan_recording.json name them.  To retire together with that recording)
     F.dcol = dcol_alias ? F.con : cv.carve(A.cf.ndense * UHC_WAVE);
     F.Y = cv.off;
     // (52 KiB, not 160 / 3 = 53.3: the LDS is handed out in granules, and 54 608 B rounded up no longer fits three times -- the tier
@@ -397,7 +404,7 @@ static bool rows_layout(Carver& cv, const UhcModelDesc& d, const KernelArgs& A, 
     cp.maxefc = maxefc; cp.maxcon = maxcon; cp.ndense = T.ncpair > 0 ? maxtwo : 0;
     cp.ld_delta = (F.LD - A.lf.LD) * 8;
     F.con = cv.carve(std::max(maxcon * UHC_CON_STRIDE, cp.ndense * UHC_WAVE));
-    F.dcol = F.con;  // the dense rows' Delassus columns are built when nothing reads the contacts any more (k_as_general)
+    F.dcol = F.con;  // (unused: see fast_layout)
     F.rowMisc = cv.carve(maxefc * 2);  // 4 ints per row; the collision pass keeps its candidate-pair list here (256 ints)
     F.ncon_nefc = cv.carve(2 + UHC_MAXTWO);  // ints: truncated flag, nefc, number of two-body rows, spare, their row ids, slot -> lane of the working set
     F.rowY = cv.carve(maxefc / 2 + 1);  // + the end of the last row

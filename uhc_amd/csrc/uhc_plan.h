@@ -34,6 +34,7 @@ struct BatchPlan {
     std::vector<short> dof_anc, m_row, m_col;
     std::vector<unsigned short> m_ij;
     std::vector<unsigned char> ncommon;
+    std::vector<unsigned long long> chainmask;  // [nv][2] bit d: dof d is on the chain of dof i (DevTopo::dof_chainmask)
     std::vector<int> pg1, pg2, cg1, cg2;  // statically filtered collision pairs: (plane, hull), (hull, hull)
     std::vector<double> model_blob;       // the models' numeric blobs, one after the other (DevNumOff::stride each)
     std::vector<unsigned int> fac_prog, sol_back, sol_fwd, chain;
