@@ -1906,6 +1906,85 @@ __device__ __forceinline__ int as_solve(const int (&Alo)[UHC_WAVE], const int (&
     return -1;
 }
 
+// The tiles of A = Yhat Yhat^T for a solve of NB row blocks (NB = dt_row_blocks(nefc), 1 .. 4), on the matrix unit: 16 x 16 tiles of v_mfma_f64_16x16x4_f64 (index
+// maps: uhc_delassus_tiles.h).  k_pgs_fast dispatches on NB once per build, so the panel loop holds no test of the block count.  For a row block J and a panel of
+// four dofs, lane l gathers Yhat[16 J + (l & 15)][4 p + (l >> 4)] from LDS (gbase / gm0 / gm1: where the row begins and the bit mask of its dofs, k_pgs_fast).  The
+// one value is the A operand of the tiles (J, .) and the B operand of the tiles (., J), so a panel gathers each row block ONCE: the panels are the outer loop and all
+// NB x NB tiles accumulate side by side, acc[I][J] += v[I] v[J]^T, the next panel's gathers issued ahead of the instructions that use this panel's.  Per tile that is
+// the sequence of instructions and operands of a build that walks the panels once per column block, panels ascending: the same bits.  Tiles of blocks >= NB are
+// not touched (the caller's 0.0).
+template <int NB>
+__device__ __forceinline__ void delassus_tiles(const KernelArgs& A, const double* S, const int (&gbase)[UHC_DT_BLOCKS], const unsigned long long (&gm0)[UHC_DT_BLOCKS],
+                                               const unsigned long long (&gm1)[UHC_DT_BLOCKS], dt_acc (&acc)[UHC_DT_BLOCKS][UHC_DT_BLOCKS]) {
+    const DevTopo& T = A.t;
+    const int npan = dt_panels(T.nv);
+    const int kq = dt_ab_k(LANE);
+    for (int h = 0; h < 2; h++) {  // dofs 0 .. 63, 64 .. 127: one word of the masks each
+        const int p0 = 16 * h, p1 = min(npan, 16 * h + 16);
+        if (p0 >= p1) break;
+        // walking state per row block: the mask from this lane's dof on, the LDS offset of the entry it stands at
+        unsigned long long rmk[NB];
+        int at[NB];
+        static_for<0, NB>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int J = decltype(jc)::value;
+            const unsigned long long wd = h ? gm1[J] : gm0[J];
+            at[J] = gbase[J] + __popcll(wd & ((1ull << kq) - 1ull)) + (h ? __popcll(gm0[J]) : 0);
+            rmk[J] = wd >> kq;
+        });
+        // (the gather runs one panel ahead, so it may stand ONE entry past its row's end -- past the last panel, and wherever the lane's dof is not
+        //  on the chain: the next row, the fast layout's slack, or the first word behind the region, all inside the LDS allocation.  What it reads
+        //  there is SELECTED away by the mask bit, never multiplied, so no value of that word -- a NaN of an earlier workgroup -- reaches A)
+        auto gather = [&](double (&v)[NB]) __attribute__((always_inline)) {
+            static_for<0, NB>([&](auto jc) __attribute__((always_inline)) {
+                constexpr int J = decltype(jc)::value;
+                const double x = S[at[J]];
+                v[J] = ((unsigned)rmk[J] & 1u) ? x : 0.0;
+                at[J] += __popc((unsigned)rmk[J] & 15u);
+                rmk[J] >>= UHC_DT_PANEL;
+            });
+        };
+        double v[NB];
+        gather(v);
+        for (int p = p0; p < p1; p++) {
+            double vn[NB];
+            gather(vn);
+            static_for<0, NB * NB>([&](auto tc) __attribute__((always_inline)) {
+                constexpr int I = decltype(tc)::value / NB, J = decltype(tc)::value % NB;
+                acc[I][J] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[I], v[J], acc[I][J], 0, 0, 0);
+            });
+            static_for<0, NB>([&](auto jc) __attribute__((always_inline)) { v[decltype(jc)::value] = vn[decltype(jc)::value]; });
+        }
+    }
+}
+// the way back of the tiles to lane = row (see delassus_tiles), column block after column block; blocks >= nblk are skipped uniformly and leave 0.0
+__device__ __forceinline__ void delassus_back(int nblk, const dt_acc (&acc)[UHC_DT_BLOCKS][UHC_DT_BLOCKS], bool valid, const FastRow& row,
+                                              int (&Alo)[UHC_WAVE], int (&Ahi)[UHC_WAVE], double& diag) {
+    static_for<0, UHC_DT_BLOCKS>([&](auto ic) __attribute__((always_inline)) {
+        constexpr int I = decltype(ic)::value;
+        if (I < nblk) {
+            static_for<0, 4>([&](auto rc) __attribute__((always_inline)) {
+                constexpr int i = decltype(rc)::value;
+                double t0 = acc[I][0][i], t1 = acc[I][1][i], t2 = acc[I][2][i], t3 = acc[I][3][i];
+                dt_swap32(t0, t2); dt_swap32(t1, t3); dt_swap16(t0, t1); dt_swap16(t2, t3);
+                const double w[4] = {t0, t1, t2, t3};  // this lane's row, columns dt_out_col(I, i, 0 .. 3)
+                static_for<0, 4>([&](auto kc) __attribute__((always_inline)) {
+                    constexpr int k2 = decltype(kc)::value, s = UHC_DT_TILE * I + 4 * i + k2;
+                    double a = w[k2];
+                    if (s == LANE && valid) { a += row.R; diag = a; }
+                    agpr_put(Alo[s], __double2loint(a));
+                    agpr_put(Ahi[s], __double2hiint(a));
+                });
+            });
+        } else {
+            static_for<0, UHC_DT_TILE>([&](auto mc) __attribute__((always_inline)) {
+                constexpr int s = UHC_DT_TILE * I + decltype(mc)::value;  // (a row >= 16 nblk >= nefc: no diagonal entry of a valid row here)
+                agpr_put(Alo[s], 0);
+                agpr_put(Ahi[s], 0);
+            });
+        }
+    });
+}
+
 // PGS with A in registers; returns the sweep count.  On exit S[L.z] = sum_r f_r Yhat_r.
 // LT: the tier whose LDS layout the rows live in (the general / large tiers solve working sets of <= 64 of their rows with the same code).
 // SL[0 .. nslot): lane that holds the dense row of slot k (an entry outside [0, nefc) = that row is not part of this solve).
@@ -1920,19 +1999,20 @@ __device__ __forceinline__ int k_pgs_fast(const KernelArgs& A, const double* mb,
         for (int k = 0; k < nslot; k++) ntwo += (unsigned)SL[k] < (unsigned)nefc;
         ntwo = __builtin_amdgcn_readfirstlane(ntwo);
     }
-    // ---- A = Yhat Yhat^T on the matrix unit, in 16 x 16 tiles of v_mfma_f64_16x16x4_f64 (index maps: uhc_delassus_tiles.h).  For a row block J and a panel
-    //      of four dofs, lane l gathers Yhat[16 J + (l & 15)][4 p + (l >> 4)] from LDS -- a packed row through the bit mask of its chain (position = chain dofs
-    //      below the dof), a dense row directly (the chain of all dofs); rows >= nefc, dofs off the chain and dofs >= nv supply 0.0.  The one value is the A
-    //      operand of the tiles (J, .) and the B operand of the tiles (., J), so dense x packed and dense x dense entries come out of the same tiles as the rest.
-    //      Column block after column block: the tiles (I, 0 .. nblk) accumulate over all panels, the next panel's gathers issued ahead of the instructions
-    //      that use them; then a 4 x 4 transposition among the lanes {g, g + 16, g + 32, g + 48} (two rounds of v_permlane32_swap / v_permlane16_swap per
-    //      register) brings lane r the columns 16 I .. 16 I + 15 of ITS row, which go to the AGPR-parked Alo / Ahi.  Blocks >= nblk are skipped uniformly.
+    // ---- A = Yhat Yhat^T on the matrix unit, in 16 x 16 tiles of v_mfma_f64_16x16x4_f64 (index maps: uhc_delassus_tiles.h).  Set-up: where the row a lane gathers
+    //      for row block J begins in LDS and which dofs it has -- a packed row lies along the chain of its last dof (its bit mask; position = chain dofs below the
+    //      dof), a dense row is the chain of all dofs; rows >= nefc supply nothing (mask 0), so do dofs off the chain and dofs >= nv.  Then the tiles, by a body
+    //      specialised on the number of row blocks (delassus_tiles<NB>: the dispatch is per wave, once per build), then the way back to lane = row (delassus_back):
+    //      a 4 x 4 transposition among the lanes {g, g + 16, g + 32, g + 48} (two rounds of v_permlane32_swap / v_permlane16_swap per register) of the tiles
+    //      (I, 0 .. 3) brings lane r the columns 16 I .. 16 I + 15 of ITS row, which go to the AGPR-parked Alo / Ahi, four columns at a time.
     int Alo[UHC_WAVE], Ahi[UHC_WAVE];  // AGPR-parked A[r][s]
     double diag = 1.0;
     {
         const int nblk = __builtin_amdgcn_readfirstlane(dt_row_blocks(nefc));
-        const int npan = dt_panels(T.nv);
-        const int kq = dt_ab_k(LANE);
+        dt_acc acc[UHC_DT_BLOCKS][UHC_DT_BLOCKS];
+        static_for<0, UHC_DT_BLOCKS * UHC_DT_BLOCKS>([&](auto tc) __attribute__((always_inline)) {
+            acc[decltype(tc)::value / UHC_DT_BLOCKS][decltype(tc)::value % UHC_DT_BLOCKS] = dt_acc{0.0, 0.0, 0.0, 0.0};
+        });
         int gbase[UHC_DT_BLOCKS];                                   // LDS offset of the operand row's first entry
         unsigned long long gm0[UHC_DT_BLOCKS], gm1[UHC_DT_BLOCKS];  // its dofs (0: the row supplies nothing)
         static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) {
@@ -1949,67 +2029,14 @@ __device__ __forceinline__ int k_pgs_fast(const KernelArgs& A, const double* mb,
                 }
             }
         });
-        static_for<0, UHC_DT_BLOCKS>([&](auto ic) __attribute__((always_inline)) {
-            constexpr int I = decltype(ic)::value;
-            double w[UHC_DT_TILE];  // this lane's row, columns 16 I ..
-            static_for<0, UHC_DT_TILE>([&](auto mc) __attribute__((always_inline)) { w[decltype(mc)::value] = 0.0; });
-            if (I < nblk) {
-                dt_acc acc[UHC_DT_BLOCKS];
-                static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) { acc[decltype(jc)::value] = dt_acc{0.0, 0.0, 0.0, 0.0}; });
-                for (int h = 0; h < 2; h++) {  // dofs 0 .. 63, 64 .. 127: one word of the masks each
-                    const int p0 = 16 * h, p1 = min(npan, 16 * h + 16);
-                    if (p0 >= p1) break;
-                    // walking state per row block: the mask from this lane's dof on, the LDS offset of the entry it stands at
-                    unsigned long long rmk[UHC_DT_BLOCKS];
-                    int at[UHC_DT_BLOCKS];
-                    static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) {
-                        constexpr int J = decltype(jc)::value;
-                        const unsigned long long wd = h ? gm1[J] : gm0[J];
-                        at[J] = gbase[J] + __popcll(wd & ((1ull << kq) - 1ull)) + (h ? __popcll(gm0[J]) : 0);
-                        rmk[J] = wd >> kq;
-                    });
-                    // (the gather runs one panel ahead, so it may stand ONE entry past its row's end -- past the last panel, and wherever the lane's dof is not
-                    //  on the chain: the next row, the fast layout's slack, or the first word behind the region, all inside the LDS allocation.  What it reads
-                    //  there is SELECTED away by the mask bit, never multiplied, so no value of that word -- a NaN of an earlier workgroup -- reaches A)
-                    auto gather = [&](double (&v)[UHC_DT_BLOCKS]) __attribute__((always_inline)) {
-                        static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) {
-                            constexpr int J = decltype(jc)::value;
-                            v[J] = 0.0;
-                            if (J < nblk) {
-                                const double x = S[at[J]];
-                                v[J] = ((unsigned)rmk[J] & 1u) ? x : 0.0;
-                                at[J] += __popc((unsigned)rmk[J] & 15u);
-                                rmk[J] >>= UHC_DT_PANEL;
-                            }
-                        });
-                    };
-                    double v[UHC_DT_BLOCKS];
-                    gather(v);
-                    for (int p = p0; p < p1; p++) {
-                        double vn[UHC_DT_BLOCKS];
-                        gather(vn);
-                        static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) {
-                            constexpr int J = decltype(jc)::value;
-                            if (J < nblk) acc[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[I], v[J], acc[J], 0, 0, 0);
-                        });
-                        static_for<0, UHC_DT_BLOCKS>([&](auto jc) __attribute__((always_inline)) { v[decltype(jc)::value] = vn[decltype(jc)::value]; });
-                    }
-                }
-                static_for<0, 4>([&](auto rc) __attribute__((always_inline)) {
-                    constexpr int i = decltype(rc)::value;
-                    double t0 = acc[0][i], t1 = acc[1][i], t2 = acc[2][i], t3 = acc[3][i];
-                    dt_swap32(t0, t2); dt_swap32(t1, t3); dt_swap16(t0, t1); dt_swap16(t2, t3);
-                    w[4 * i + 0] = t0; w[4 * i + 1] = t1; w[4 * i + 2] = t2; w[4 * i + 3] = t3;  // columns dt_out_col(I, i, 0 .. 3)
-                });
-            }
-            static_for<0, UHC_DT_TILE>([&](auto mc) __attribute__((always_inline)) {
-                constexpr int m = decltype(mc)::value, s = UHC_DT_TILE * I + m;
-                double a = w[m];
-                if (s == LANE && valid) { a += row.R; diag = a; }
-                agpr_put(Alo[s], __double2loint(a));
-                agpr_put(Ahi[s], __double2hiint(a));
-            });
-        });
+        switch (nblk) {
+            case 0: break;
+            case 1: delassus_tiles<1>(A, S, gbase, gm0, gm1, acc); break;
+            case 2: delassus_tiles<2>(A, S, gbase, gm0, gm1, acc); break;
+            case 3: delassus_tiles<3>(A, S, gbase, gm0, gm1, acc); break;
+            default: delassus_tiles<4>(A, S, gbase, gm0, gm1, acc); break;
+        }
+        delassus_back(nblk, acc, valid, row, Alo, Ahi, diag);
     }
     PROF(10)
     const bool any_fric = wave_or(row.type == ROW_FRICTION ? 1 : 0) != 0;
