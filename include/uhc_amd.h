@@ -616,7 +616,8 @@ int32_t uhc_eval_metrics(void* stream, int32_t n_env, int32_t n_body, int32_t nq
 
 /* ------------------------------------------------------------------ contact quality of a motion: penetration, skate, float, contact count
  * compute_penetration / compute_skate (uhc/smpllib/smpl_eval.py:125-149) on the device.  The reference scores SMPL surface vertices; this library scores the
- * convex-hull vertices every compiled model carries in the body frame (mesh hulls; sphere and capsule cores with their radius) -- a DEVIATION -- and adds
+ * convex-hull vertices every compiled model carries in the body frame (mesh hulls; sphere and capsule cores with their radius) -- a DEVIATION; the SMPL
+ * vertices themselves are uhc_smpl_mesh's, below, from the caller's own model files -- and adds
  * `float`, which the reference does not have.  Same conventions as the evaluation functions above: `stream` is a hipStream_t (NULL = the default stream),
  * every argument is checked before the first HIP call, reductions have a fixed order and no floating-point atomics (two runs are bit-identical), no index or
  * counter, whatever it holds, sends a read or a write outside the arrays.  (Purely additive: UHC_ABI_VERSION stays 11.)
@@ -654,6 +655,44 @@ int32_t uhc_surface_metrics(void* stream, const UhcSurface* surf, int32_t n_seq,
                             int64_t n_rows_total, double floor_z, double* d_row_out, double* d_seq_means, int32_t* d_bad, int32_t* h_bad);
 int32_t uhc_eval_record_pose(void* stream, int32_t phase, int32_t n_env, int32_t nbody, int32_t row_cap, const double* d_xpos, const double* d_xquat,
                              const int32_t* d_done, const int32_t* d_alive, const int32_t* d_rows, double* d_pose);
+
+/* ------------------------------------------------------------------ the SMPL body mesh: vertices, joints and contact quality on SMPL vertices
+ * SMPL_Parser.get_joints_verts (uhc/smpllib/smpl_parser.py:335-360: smplx's lbs) and compute_penetration / compute_skate on its vertices
+ * (uhc/smpllib/smpl_eval.py:113-149) as one fused kernel, float64.  The SMPL tables come from the caller's own (licensed) model files; nothing of them is
+ * shipped.  Same conventions as the functions above: `stream` is a hipStream_t (NULL = the default stream), every argument is checked before the first HIP
+ * call, reductions have a fixed order and no floating-point atomics (two runs are bit-identical), no index or counter, whatever it holds, sends a read or a
+ * write outside the arrays.  (Purely additive: UHC_ABI_VERSION stays 11.)
+ *
+ *   R_j      = I + sin(a) K + (1 - cos(a)) K K,  a = |r_j + 1e-8| (1e-8 added to each component, as smplx), K = skew(r_j / a): exactly I at r_j = 0
+ *   v_shaped = v_template + shapedirs beta;  J = J_regressor v_shaped                                   (per sequence)
+ *   v_posed  = v_shaped + posedirs feature,  feature = (R_1 .. R_23 - I) row-major, 207 numbers         (on v_mfma_f64_16x16x4_f64)
+ *   G_j      = chain over the parents of [R_j | J_j - J_parent(j)];  A_j = [G_j.R | G_j.t - G_j.R J_j]
+ *   vertex   = (sum_j w[v][j] A_j) [v_posed; 1] + trans;  joint_j = G_j.t + trans
+ * and, with h = vertex.z - floor_z and radius 0, the four values of uhc_surface_metrics (pen, skate, float, contact: same definitions, units, strict /
+ * non-strict predicates and T / T - 1 / T / T means), plus the lowest vertex z of a row.
+ *
+ * uhc_smpl_mesh_create copies the tables of n_models bodies (the genders) that share n_vert and the 24-joint tree to the current device, in the layout the
+ *   kernel reads: h_v_template [n_models][n_vert][3], h_shapedirs [..][n_vert][3][10], h_posedirs [..][n_vert][3][207], h_J_regressor [..][24][n_vert],
+ *   h_weights [..][n_vert][24], h_parents int32 [24] (parent[0] = -1).  Refused: n_vert outside 1 .. 65535, n_models < 1, a parent table that is
+ *   no tree rooted at joint 0 with parent[j] < j, a non-finite table entry.  A handle serves one stream at a time: it owns what a call keeps between its
+ *   kernels, and a call that needs more of it than any call before frees and allocates inside the call (hipFree / hipMalloc: not under stream capture; a
+ *   first call of the largest shape outside the capture settles it).
+ * uhc_smpl_mesh: rows are addressed as in uhc_surface_metrics (d_seq_start, d_seq_rows clamped to 0 .. row_cap, d_seq_model, n_rows_total); the pose of a
+ *   global row lies at d_pose_aa + row * pose_stride as [72], its translation at d_trans + row * trans_stride as [3] (strides in doubles: uhc_qpos_smpl's
+ *   outputs are read where they lie); d_betas [n_seq][10].
+ *   Outputs, each may be NULL (not all): d_vert [n_rows_total][n_vert][3], d_joints [n_rows_total][24][3], d_row_out [n_rows_total][4], d_seq_means
+ *   [n_seq][4], d_row_zmin [n_rows_total].  Slots of rows outside every sequence are left untouched.
+ *   d_bad int32 [1]: set by the call to the number of rows with a non-finite pose or translation (NaN in every output of the row and in the skate of the
+ *   row before it) plus the number of sequences whose rows would leave 0 .. n_rows_total (skipped: nothing of them is read or written).
+ *   h_bad (HOST, may be NULL): when given, the call waits for the stream and stores d_bad's count there.  n_seq == 0 succeeds and launches nothing. */
+typedef struct UhcSmplMesh UhcSmplMesh;
+int32_t uhc_smpl_mesh_create(int32_t n_vert, int32_t n_models, const double* h_v_template, const double* h_shapedirs, const double* h_posedirs,
+                             const double* h_J_regressor, const double* h_weights, const int32_t* h_parents, UhcSmplMesh** out);
+void uhc_smpl_mesh_free(UhcSmplMesh* mesh);
+int32_t uhc_smpl_mesh(void* stream, UhcSmplMesh* mesh, int32_t n_seq, const int64_t* d_seq_start, const int32_t* d_seq_rows, int32_t row_cap,
+                      const int32_t* d_seq_model, const double* d_betas, const double* d_pose_aa, int64_t pose_stride, const double* d_trans,
+                      int64_t trans_stride, int64_t n_rows_total, double floor_z, double* d_vert, double* d_joints, double* d_row_out,
+                      double* d_seq_means, double* d_row_zmin, int32_t* d_bad, int32_t* h_bad);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

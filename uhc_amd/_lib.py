@@ -25,6 +25,7 @@ SYMBOLS = [
     "uhc_surface_create", "uhc_surface_free", "uhc_surface_metrics", "uhc_eval_record_pose",
     "uhc_qpos_smpl", "uhc_smpl6d_qpos",
     "uhc_env_live_slide", "uhc_env_live_window",
+    "uhc_smpl_mesh_create", "uhc_smpl_mesh_free", "uhc_smpl_mesh",
 ]
 
 
@@ -121,6 +122,12 @@ def lib():
         L.uhc_env_live_slide.argtypes = [P, I]
         L.uhc_env_live_window.argtypes = [P, C.POINTER(P), C.POINTER(P)]
         L.uhc_env_live_slide.restype = L.uhc_env_live_window.restype = I
+    if hasattr(L, "uhc_smpl_mesh"):  # (additive within ABI 11)
+        L.uhc_smpl_mesh_create.argtypes = [I, I, P, P, P, P, P, P, C.POINTER(P)]
+        L.uhc_smpl_mesh_free.argtypes = [P]
+        L.uhc_smpl_mesh_free.restype = None
+        L.uhc_smpl_mesh.argtypes = [P, P, I, P, P, I, P, P, P, C.c_int64, P, C.c_int64, C.c_int64, D, P, P, P, P, P, P, C.POINTER(I)]
+        L.uhc_smpl_mesh_create.restype = L.uhc_smpl_mesh.restype = I
     _lib = L
     return L
 

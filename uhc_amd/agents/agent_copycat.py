@@ -410,6 +410,43 @@ def _smpl_params_host(ev, res, model_index):
     return out
 
 
+def _eval_mesh_setup(self, loader, device=None):
+    """cfg.eval_mesh (the directory of the user's own SMPL model files): the models of the genders the loader's clips name, each clip's (beta [10], index into
+    those models) and -- device given -- the handle of the mesh kernel over them.  Cached per (directory, loader)."""
+    from ..smpllib.smpl_mesh import MeshBodyProvider, gender_index
+    cache = self.__dict__.setdefault("_eval_meshes", {})
+    key = (str(self.cfg.eval_mesh), loader.name)
+    if key not in cache:
+        provider = MeshBodyProvider(str(self.cfg.eval_mesh))
+        genders = sorted({gender_index(loader.data["gender"][k]) for k in loader.data_keys})
+        models = [provider.model(g) for g in genders]
+        clip = {}
+        for k in loader.data_keys:
+            beta = np.asarray(loader.data["beta"][k], dtype=np.float64)
+            clip[k] = ((beta[0] if beta.ndim == 2 else beta)[:10].copy(), genders.index(gender_index(loader.data["gender"][k])))
+        cache[key] = dict(models=models, clip=clip, handle=None)
+    m = cache[key]
+    if device is not None and m["handle"] is None:
+        from .. import eval_ops as EO
+        with torch.cuda.device(device):
+            m["handle"] = EO.SmplMesh(m["models"])
+    return m
+
+
+def _mesh_vertices_host(ev, res, model_index, mesh, key):
+    """cfg.eval_mesh on the host: the clip's predicted rows as SMPL poses (qpos_to_smpl on its own body shape), then lbs_numpy on its own beta and gender ->
+    the (T, 6890, 3) vertices compute_metrics scores and drops."""
+    from ..smpllib.smpl_mesh import lbs_numpy
+    from ..smpllib.smpl_mujoco import qpos_quat_to_smpl, qpos_to_smpl
+    kin = ev.body_models[model_index]
+    if ev.use_quat:
+        pose, trans = qpos_quat_to_smpl(res["pred"], kin)
+    else:
+        pose, trans = qpos_to_smpl(res["pred"], kin, smpl_model=ev.cc_cfg.robot_cfg.get("model", "smpl"))
+    beta, g = mesh["clip"][key]
+    return lbs_numpy(mesh["models"][g], np.asarray(pose).reshape(-1, 72), beta, trans)[0]
+
+
 @torch.no_grad()
 def _eval_seqs(self, take_keys, loader):
     """Run the mean-action policy over whole clips (eval_seq, agent_copycat.py:438-494), all clips of a chunk at once.  With cfg.eval_smpl every clip's
@@ -437,6 +474,7 @@ def _eval_seqs(self, take_keys, loader):
         return _eval_seqs_device(self, ev, take_keys, loader, n)
     surf = bool(getattr(cfg, "eval_surface", False))  # contact quality on the hull vertices: the loop also keeps xpos / xquat of bodies 1 .. body_lim - 1
     smpl = bool(getattr(cfg, "eval_smpl", False))  # the motion handed back as SMPL parameters: pred_pose_aa / pred_trans / gt_pose_aa / gt_trans per clip
+    mesh = _eval_mesh_setup(self, loader) if getattr(cfg, "eval_mesh", False) else None  # contact quality on the SMPL vertices of the clip's own beta and gender
     if surf:
         from ..smpllib.smpl_eval import hull_vertices, surface_tables
         tables = [surface_tables(bm, ev.body_lim) for bm in ev.body_models]
@@ -526,6 +564,8 @@ def _eval_seqs(self, take_keys, loader):
             if surf:  # compute_metrics scores the vertices and drops them again
                 pz = np.vstack(poses[e])
                 res["pred_vertices"] = hull_vertices(tables[int(clip_model.get(k, 0))], pz[:, :3 * (bl - 1)], pz[:, 3 * (bl - 1):])
+            if mesh:
+                res["pred_vertices"] = _mesh_vertices_host(ev, res, int((getattr(self, "_clip_model", None) or {}).get(k, 0)), mesh, k)
             res.update(compute_metrics(res, None))
             if smpl:
                 res.update(_smpl_params_host(ev, res, int((getattr(self, "_clip_model", None) or {}).get(k, 0))))
@@ -557,10 +597,15 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
                 surface = self._eval_surfaces[id(ev)] = EO.Surface(list(ev.body_models), body_lim=ev.body_lim)
         clip_model = getattr(self, "_clip_model", None) or {}
     smpl = bool(getattr(cfg, "eval_smpl", False))  # the motion as SMPL parameters: one uhc_qpos_smpl launch reads the record, one (once per bank) the bank
+    # contact quality on the SMPL vertices of each clip's own beta and gender: uhc_qpos_smpl reads the record, uhc_smpl_mesh its poses; the four values travel as the
+    # hull vertices' do (the config refuses both at once)
+    mesh = _eval_mesh_setup(self, loader, dev) if getattr(cfg, "eval_mesh", False) else None
+    cq = surf or mesh is not None
     gt_smpl = None
-    if smpl:
+    if smpl or mesh:
         clip_model = getattr(self, "_clip_model", None) or {}
         models = list(ev.body_models)
+    if smpl:
         if not ev.use_quat:  # (the ball-joint humanoid's bank keeps the expert's joint quaternions elsewhere: pred_* alone)
             self._eval_smpl_banks = getattr(self, "_eval_smpl_banks", {})
             gt_smpl = self._eval_smpl_banks.get(id(ev))
@@ -623,12 +668,19 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
             block = 16
 
         row_metrics, _, bad = EO.metrics(rec, frames)
-        if surf or smpl:
+        if cq or smpl:
             seq_model = torch.zeros(n, dtype=torch.int32, device=dev)
             seq_model[:m] = torch.tensor([int(clip_model.get(k, 0)) for k in keys], dtype=torch.int32).to(dev)
         if surf:
             srow, smeans, sbad = EO.surface_metrics_of_record(surface, rec, seq_model=seq_model)
             bad = bad + sbad  # (a non-finite pose: the same refusal below)
+        if mesh:
+            betas = torch.zeros(n, 10, dtype=torch.float64, device=dev)
+            betas[:m] = torch.from_numpy(np.stack([mesh["clip"][k][0] for k in keys])).to(dev)
+            gender = [mesh["clip"][k][1] for k in keys] + [0] * (n - m)
+            mres = EO.mesh_metrics_of_record(mesh["handle"], rec, models, betas, seq_model=seq_model, seq_gender=gender)
+            srow, smeans = mres["row_out"], mres["seq_means"]
+            bad = bad + mres["bad"]  # (a quaternion that cannot be normalised, a non-finite pose: the same refusal below)
         if smpl:
             p_pose, p_trans, pbad = EO.smpl_of_record(rec, models, seq_model=seq_model)
             bad = bad + pbad  # (a recorded quaternion of zero or non-finite norm: the same refusal below)
@@ -637,21 +689,21 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
         rmask, smask = ar < rec.rows[:, None], ar < rec.steps[:, None]
         gi = rec.gt_frame[rmask].clamp(0, frames.shape[0] - 1)
         g = frames[gi]
-        rows_d = torch.cat([rec.pred_qpos[rmask], rec.pred_jpos[rmask], g[:, 0:76], g[:, 151:223], row_metrics[rmask]] + ([srow[rmask][:, 3:4]] if surf else []) +
+        rows_d = torch.cat([rec.pred_qpos[rmask], rec.pred_jpos[rmask], g[:, 0:76], g[:, 151:223], row_metrics[rmask]] + ([srow[rmask][:, 3:4]] if cq else []) +
                            ([p_pose[rmask], p_trans[rmask]] if smpl else []) + ([gt_smpl[1][gi], gt_smpl[2][gi]] if gt_smpl else []), 1)
-        words = torch.stack([rec.rows.double(), rec.steps.double(), rec.fail_safe.double(), rec.percent] + ([smeans[:, i] for i in range(3)] if surf else []), 1)
+        words = torch.stack([rec.rows.double(), rec.steps.double(), rec.fail_safe.double(), rec.percent] + ([smeans[:, i] for i in range(3)] if cq else []), 1)
         flat = torch.cat([words.reshape(-1), rec.overflow.double(), bad.double(), rows_d.reshape(-1), rec.rewards[smask]]).cpu().numpy()
-        nw = 4 + (3 if surf else 0)  # per-env words: rows, steps, fail_safe, percent (+ the clip's mean pentration, skate, float)
+        nw = 4 + (3 if cq else 0)  # per-env words: rows, steps, fail_safe, percent (+ the clip's mean pentration, skate, float)
         words = flat[:nw * n].reshape(n, nw)
         flat = flat[nw * n - 4 * n:]  # (what follows is indexed as it always was)
         overflow, n_bad = int(flat[4 * n]), int(flat[4 * n + 1])
         if overflow:
             raise RuntimeError(f"eval_seqs: {overflow} trajectory rows did not fit the record (row_cap {rec.row_cap})")
         if n_bad:
-            raise RuntimeError(f"eval_seqs: {n_bad} recorded expert frame indices lie outside the clip bank" + (" or recorded body poses are not finite" if surf else "") +
+            raise RuntimeError(f"eval_seqs: {n_bad} recorded expert frame indices lie outside the clip bank" + (" or recorded body poses are not finite" if cq else "") +
                                (" or recorded quaternions cannot be normalised" if smpl else ""))
         n_rows, n_steps = words[:, 0].astype(int), words[:, 1].astype(int)
-        W0 = ql + 72 + 76 + 72 + nm + (1 if surf else 0)  # where the SMPL parameters start: 75 columns for pred, 75 for gt
+        W0 = ql + 72 + 76 + 72 + nm + (1 if cq else 0)  # where the SMPL parameters start: 75 columns for pred, 75 for gt
         W = W0 + (75 if smpl else 0) + (75 if gt_smpl else 0)
         rows_h = flat[4 * n + 2:4 * n + 2 + n_rows.sum() * W].reshape(-1, W)
         rew_h = flat[4 * n + 2 + n_rows.sum() * W:]
@@ -665,7 +717,7 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
             for i, name in enumerate(EO.METRICS):  # numpy's lengths: T rows, T - 1 for the velocity, T - 2 for the acceleration
                 res[name] = rw[:max(T - (1 if name == "vel_dist" else 2 if name == "accel_dist" else 0), 0), ql + 220 + i].copy()
             res["succ"] = np.array([(not res["fail_safe"]) and res["percent"] == 1])
-            if surf:
+            if cq:
                 res["pentration"], res["skate"], res["float"] = (np.float64(words[e, 4 + i]) for i in range(3))
                 res["contact"] = rw[:, ql + 220 + nm].copy()
             if smpl:

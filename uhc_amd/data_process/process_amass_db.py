@@ -7,7 +7,8 @@ annotations `sample_data/amass_copycat_occlusion_v2.pkl` {"0-" + name: {issue, i
     any other issue -> dropped;  sequences shorter than 10 frames -> dropped;
   * height fix (fix_height_smpl_vanilla, :199-219): shift trans z so that the lowest SMPL vertex of frame 0 touches z = 0:
     `fix_height=uhc_amd.smpllib.smpl_robot.make_fix_height(body_provider)` (SMPLBody over the licensed SMPL files, which this image
-    lacks, or any (betas, gender) -> (vertices, joints, skin weights) provider; linear blend skinning without the pose blend shapes);
+    lacks, or any (betas, gender) -> (vertices, joints, skin weights) provider; linear blend skinning without the pose blend shapes on
+    the host, with them -- make_fix_height(MeshBodyProvider, device=True), what --smpl_dir uses when a GPU is present -- through uhc_smpl_mesh);
     without the hook trans is kept and the fact is recorded under key "height_fixed": False;
   * pose_6d = first two columns of every joint's rotation matrix, float32 like the reference's convert_aa_to_orth6d
     (uhc/utils/transform_utils.py:91-100, 76-78).
@@ -117,10 +118,19 @@ if __name__ == "__main__":
     np.random.shuffle(qpos_list)
     fix = None
     try:
+        import torch
         from ..smpllib.smpl_robot import SMPLBody, make_fix_height
-        body = SMPLBody(args.smpl_dir)
-        body._load(0)
-        fix = make_fix_height(body)
+        # with a GPU: the reference's own height -- the first frame through the mesh kernel, pose blend shapes included.  One row per call is the kernel's
+        # slowest shape (~16 ms a clip); the gain over the host fix is the blend shapes' millimetres, not time
+        if torch.cuda.is_available():
+            from ..smpllib.smpl_mesh import MeshBodyProvider
+            body = MeshBodyProvider(args.smpl_dir)
+            body.model(0)
+            fix = make_fix_height(body, device=True)
+        else:
+            body = SMPLBody(args.smpl_dir)
+            body._load(0)
+            fix = make_fix_height(body)
     except (FileNotFoundError, ImportError) as e:
         print(f"no height fix ({e})")
     train, test, valid = split_amass(process_qpos_list(qpos_list, joblib.load(args.occlusion), fix_height=fix))

@@ -207,3 +207,126 @@ def surface_metrics_of_bank(surface, frames, clip_start, clip_len, clip_model=No
     rows = torch.as_tensor(clip_len).to(dev, torch.int32).contiguous()
     model = None if clip_model is None else torch.as_tensor(clip_model).to(dev, torch.int32).contiguous()
     return surface_metrics(surface, frames[:, FR_WBPOS:FR_WBPOS + 3 * N_BODY], frames[:, FR_WBQUAT:FR_WBQUAT + 4 * N_BODY], start, rows, seq_model=model, **kw)
+
+
+# ------------------------------------------------------------------ the SMPL body mesh (uhc_amd/csrc/uhc_smpl_mesh.hip)
+MESH_WANT = ("vertices", "joints", "metrics", "rows", "means", "zmin")
+
+
+class SmplMesh:
+    """The tables of one or several SMPL models (smpllib.smpl_mesh.load_smpl_model: the genders; they share the vertex count and the joint tree) on the
+    current device, in the layout uhc_smpl_mesh reads.  The handle also owns what a call keeps between its kernels: use it on one stream at a time.  A call
+    with more sequences (or, for means without rows, more rows) than any before it frees and allocates that space inside the call, so it cannot be
+    captured into a graph; a first call of the largest shape outside the capture settles it."""
+
+    def __init__(self, models):
+        import numpy as np
+        models = list(models) if isinstance(models, (list, tuple)) else [models]
+        if not models:
+            raise ValueError("SmplMesh: no model")
+        V = int(models[0]["v_template"].shape[0])
+        for i, m in enumerate(models[1:], 1):
+            if m["v_template"].shape[0] != V:
+                raise ValueError(f"SmplMesh: model {i} has {m['v_template'].shape[0]} vertices, model 0 has {V} (one topology expected)")
+            if not np.array_equal(m["parents"], models[0]["parents"]):
+                raise ValueError(f"SmplMesh: model {i} has another joint tree than model 0")
+        self.n_vert, self.n_models, self.models = V, len(models), models
+        stack = lambda k: np.ascontiguousarray(np.stack([np.asarray(m[k], dtype=np.float64) for m in models]))
+        tabs = [stack(k) for k in ("v_template", "shapedirs", "posedirs", "J_regressor", "weights")]
+        parents = np.ascontiguousarray(models[0]["parents"], dtype=np.int32)
+        h = C.c_void_p()
+        self._L = lib()
+        check(self._L.uhc_smpl_mesh_create(V, self.n_models, *[t.ctypes.data_as(C.c_void_p) for t in tabs], parents.ctypes.data_as(C.c_void_p), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.uhc_smpl_mesh_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def smpl_mesh(mesh, pose_aa, trans, seq_start, seq_rows, betas, seq_model=None, want=("metrics",), floor_z=0.0, wait=False, row_cap=None, out=None):
+    """Posed SMPL bodies on the device -> {name: tensor} for the names of `want` plus "bad":
+      "vertices" [n_rows][V][3], "joints" [n_rows][24][3], "rows" -> "row_out" [n_rows][4] and "means" -> "seq_means" [n_seq][4] (SURFACE_METRICS order, mm,
+      on SMPL vertices; "metrics" asks for both), "zmin" [n_rows]: the lowest vertex z of each row.
+    pose_aa [n_rows][>= 72], trans [n_rows][>= 3]: 2-D float64 device views with unit inner stride, read where they lie (qpos_smpl_device's outputs flattened
+    over their leading dimensions); seq_start int64 / seq_rows int32 [n_seq] as for surface_metrics (row_cap None: max(seq_rows), which reads it back);
+    betas float64 [n_seq][10]; seq_model int32 [n_seq] or None: which of the mesh's models (genders) a sequence is.  Slots of rows outside every sequence
+    keep what they held (NaN in a tensor made here; `out`: {key: tensor} to write into).  bad: an int32 [1] device tensor, or -- wait=True, the call then
+    waits for the stream -- the int itself: rows with a non-finite pose or translation (NaN throughout) plus sequences outside the rows (skipped)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in MESH_WANT for w in want):
+        raise ValueError(f"smpl_mesh: want names any of {MESH_WANT}, got {want!r}")
+    assert pose_aa.dtype == trans.dtype == betas.dtype == torch.float64 and pose_aa.dim() == trans.dim() == 2 and pose_aa.shape[0] == trans.shape[0]
+    assert (pose_aa.numel() == 0 or pose_aa.stride(1) == 1) and (trans.numel() == 0 or trans.stride(1) == 1) and pose_aa.shape[1] >= 3 * N_BODY and trans.shape[1] >= 3
+    assert seq_start.dtype == torch.int64 and seq_rows.dtype == torch.int32 and seq_start.is_contiguous() and seq_rows.is_contiguous()
+    n_seq, n_rows, dev = seq_start.numel(), pose_aa.shape[0], pose_aa.device
+    assert seq_rows.numel() == n_seq and (seq_model is None or (seq_model.dtype == torch.int32 and seq_model.is_contiguous() and seq_model.numel() == n_seq))
+    assert betas.is_contiguous() and betas.shape == (n_seq, 10)
+    if row_cap is None:
+        row_cap = max(int(seq_rows.max().item()), 1) if n_seq else 1
+    shapes = {"vertices": (n_rows, mesh.n_vert, 3), "joints": (n_rows, N_BODY, 3), "row_out": (n_rows, len(SURFACE_METRICS)), "seq_means": (n_seq, len(SURFACE_METRICS)),
+              "zmin": (n_rows,)}
+    keys = [k for k, on in (("vertices", "vertices" in want), ("joints", "joints" in want), ("row_out", "metrics" in want or "rows" in want),
+                            ("seq_means", "metrics" in want or "means" in want), ("zmin", "zmin" in want)) if on]
+    res = {}
+    for k in keys:
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.full(shapes[k], float("nan"), dtype=torch.float64, device=dev)
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shapes[k], k
+        res[k] = t
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n_seq == 0:  # nothing to launch (and empty tensors have no address to hand over)
+        res["bad"] = 0 if wait else bad
+        return res
+    h_bad = C.c_int32(0)
+    ps, ts = (pose_aa.stride(0) if n_rows > 1 else pose_aa.shape[1]), (trans.stride(0) if n_rows > 1 else trans.shape[1])
+    check(lib().uhc_smpl_mesh(_stream(pose_aa), mesh._h, n_seq, _p(seq_start), _p(seq_rows), int(row_cap), _p(seq_model), _p(betas), _p(pose_aa), ps, _p(trans), ts,
+                              n_rows, float(floor_z), _p(res.get("vertices")), _p(res.get("joints")), _p(res.get("row_out")), _p(res.get("seq_means")),
+                              _p(res.get("zmin")), _p(bad), C.byref(h_bad) if wait else None))
+    res["bad"] = int(h_bad.value) if wait else bad
+    return res
+
+
+def _mesh_seq(betas, seq_gender, n_seq, dev):
+    b = torch.as_tensor(betas).to(dev, torch.float64).reshape(-1, torch.as_tensor(betas).shape[-1])[:, :10]
+    b = (b.expand(n_seq, 10) if b.shape[0] == 1 else b).contiguous()
+    g = None if seq_gender is None else torch.as_tensor(seq_gender).to(dev, torch.int32).contiguous()
+    return b, g
+
+
+def mesh_metrics_of_record(mesh, rec, models, betas, seq_model=None, seq_gender=None, want=("metrics",), **kw):
+    """The contact quality of every env's recorded motion on SMPL vertices: smpl_of_record (rec.pred_qpos -> pose_aa, trans on the device), then smpl_mesh
+    on them where they lie -- no pose leaves the device.  models / seq_model: the compiled humanoid model(s) and each env's body shape, as for
+    smpl_of_record; betas [n_env][10 | 16] (or one row for all) and seq_gender [n_env] or None: each env's SMPL shape and which of the mesh's models it is.
+    -> smpl_mesh's dict, the row tensors as [n_env][row_cap][...]; "bad" adds the rows smpl_of_record found bad when both are counts (wait=True)."""
+    pose_aa, trans, bad0 = smpl_of_record(rec, models, seq_model=seq_model, wait=bool(kw.get("wait", False)))
+    n, dev = rec.n_env * rec.row_cap, pose_aa.device
+    b, g = _mesh_seq(betas, seq_gender, rec.n_env, dev)
+    start = torch.arange(rec.n_env, dtype=torch.int64, device=dev) * rec.row_cap
+    res = smpl_mesh(mesh, pose_aa.view(n, 72), trans.view(n, 3), start, rec.rows, b, seq_model=g, want=want, row_cap=rec.row_cap, **kw)
+    for k in ("vertices", "joints", "row_out", "zmin"):
+        if k in res:
+            res[k] = res[k].view((rec.n_env, rec.row_cap) + tuple(res[k].shape[1:]))
+    res["bad"] = res["bad"] + bad0
+    return res
+
+
+def mesh_metrics_of_bank(mesh, frames, clip_start, clip_len, models, betas, clip_model=None, clip_gender=None, want=("metrics",), **kw):
+    """The counterpart for the expert clips themselves: smpl_of_bank on the bank's qpos columns (hinge rows), then smpl_mesh with one sequence per clip.
+    -> smpl_mesh's dict over [n_frames] rows and [n_clips] sequences."""
+    pose_aa, trans, bad0 = smpl_of_bank(frames, clip_start, models, clip_model=clip_model, wait=bool(kw.get("wait", False)))
+    dev = frames.device
+    start = torch.as_tensor(clip_start).to(dev, torch.int64).contiguous()
+    rows = torch.as_tensor(clip_len).to(dev, torch.int32).contiguous()
+    b, g = _mesh_seq(betas, clip_gender, start.numel(), dev)
+    res = smpl_mesh(mesh, pose_aa, trans, start, rows, b, seq_model=g, want=want, **kw)
+    res["bad"] = res["bad"] + bad0
+    return res

@@ -263,3 +263,12 @@ def smpl_6d_to_qpose(full_pose, model, normalize=False):
     R = np.stack([x, np.cross(z, x), z], axis=-1)
     pose_aa = sRot.from_matrix(R.reshape(-1, 3, 3)).as_rotvec().reshape(full_pose.shape[0], -1)
     return smpl_to_qpose(pose_aa, model, trans=full_pose[:, :3], normalize=normalize)
+
+
+def __getattr__(name):
+    # `from uhc.smpllib.smpl_parser import SMPL_Parser` resolves here (uhc/__init__.py aliases that module onto this one); the class lives in smpl_mesh, which
+    # imports this module's tables -- hence on first use, not at import
+    if name == "SMPL_Parser":
+        from .smpl_mesh import SMPL_Parser
+        return SMPL_Parser
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

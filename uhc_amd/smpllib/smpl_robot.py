@@ -89,11 +89,17 @@ def pose_body(verts, joints, skin_weights, pose_aa):
     return np.einsum("vab,vb->va", T[:, :3, :3], v) + T[:, :3, 3]
 
 
-def make_fix_height(body_provider: Callable):
+def make_fix_height(body_provider: Callable, device: bool = False):
     """fix_height_smpl_vanilla (uhc/data_process/process_amass_db.py:194-219): shift the clip so that the lowest vertex of its FIRST frame
     touches z = 0.  -> callable (pose_aa (T, 72), betas, trans (T, 3), gender) -> trans, the `fix_height=` hook of process_qpos_list.
-    body_provider: SMPLBody (the licensed files) or any (betas, gender) -> (vertices, joints, skin weights)."""
+    body_provider: SMPLBody (the licensed files) or any (betas, gender) -> (vertices, joints, skin weights).
+    device=True: the first frame goes through the mesh kernel instead (uhc_smpl_mesh's lowest vertex of a row), pose blend shapes included -- the
+    height the reference computes; body_provider is then a smpl_mesh.MeshBodyProvider (the full model files).  It needs a GPU; the default needs none.
+    One row is the kernel's worst case (a single wave walks every vertex tile: ~16 ms a clip on an MI355X, where smpl_mesh.lbs_numpy gives the same height
+    in ~2 ms on the host): the variant is for callers whose poses already lie on the device, not a faster data-set pass."""
     names = {"neutral": 0, "male": 1, "female": 2}
+    if device:
+        return _make_fix_height_device(body_provider)
 
     def fix(pose_aa, betas, trans, gender):
         g = gender.item() if isinstance(gender, np.ndarray) else gender
@@ -104,6 +110,31 @@ def make_fix_height(body_provider: Callable):
         v0 = pose_body(verts, joints, W, np.asarray(pose_aa)[0]) + np.asarray(trans, dtype=np.float64)[0]
         out = np.array(trans, dtype=np.float64, copy=True)
         out[:, 2] -= v0[:, 2].min()
+        return out
+
+    return fix
+
+
+def _make_fix_height_device(provider):
+    import torch
+    from .. import eval_ops as EO
+    from .smpl_mesh import gender_index
+    if not hasattr(provider, "model"):
+        raise ValueError("make_fix_height(device=True) takes a smpl_mesh.MeshBodyProvider: the pose blend shapes come from the full model files")
+    meshes = {}
+
+    def fix(pose_aa, betas, trans, gender):
+        g = gender_index(gender)
+        if g not in meshes:
+            meshes[g] = EO.SmplMesh([provider.model(g)])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        up = lambda a, n: torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)[:n])).to(dev).view(1, n)
+        res = EO.smpl_mesh(meshes[g], up(np.asarray(pose_aa)[0], 72), up(np.asarray(trans)[0], 3), torch.zeros(1, dtype=torch.int64, device=dev),
+                           torch.ones(1, dtype=torch.int32, device=dev), up(betas, 10), want=("zmin",), row_cap=1, wait=True)
+        if res["bad"]:
+            raise ValueError("fix_height: the clip's first frame holds a non-finite pose or translation")
+        out = np.array(trans, dtype=np.float64, copy=True)
+        out[:, 2] -= float(res["zmin"][0].item())
         return out
 
     return fix

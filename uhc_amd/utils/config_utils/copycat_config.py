@@ -120,6 +120,15 @@ class Config(Base_Config):
         self.eval_smpl = g("eval_smpl", False)
         if not isinstance(self.eval_smpl, bool):
             raise ValueError(f"eval_smpl: true or false, got {self.eval_smpl!r}")
+        # contact quality on the SMPL surface, as the reference scores it (smpl_eval.py:113-149): false (default: eval_seqs returns what it always returned), or the
+        # directory of the user's own SMPL model files (SMPL_NEUTRAL / _MALE / _FEMALE .npz | .pkl; licensed, not shipped).  Every clip's result then carries
+        # pentration / skate / float / contact on the 6 890 vertices of ITS beta and gender: with eval_build "device" from uhc_qpos_smpl + uhc_smpl_mesh on the record,
+        # with "host" from qpos_to_smpl + lbs_numpy + compute_*.  The keys are eval_surface's: one of the two at a time
+        self.eval_mesh = g("eval_mesh", False)
+        if not (self.eval_mesh is False or (isinstance(self.eval_mesh, str) and self.eval_mesh)):
+            raise ValueError(f"eval_mesh: false or the directory of the SMPL model files, got {self.eval_mesh!r}")
+        if self.eval_mesh and self.eval_surface:
+            raise ValueError("eval_mesh and eval_surface write the same result keys (pentration, skate, float, contact): set one of them")
         self.ppo_dtype = g("ppo_dtype", "float64")
         # data-parallel gradient exchange: the dtype on the wire.  float32 (default): SURVEY 8e's 32 MB per optimisation epoch; the local
         # gradient means travel scaled by the rank's sample count and are divided by the global count in the parameters' own float64, so the
