@@ -26,6 +26,14 @@ PROBE_API int uhc_surface_probe_seq(int n_body, int n_vert, const int* vert_body
     return bad;
 }
 
+// the finished row as the kernels and the loop above store it (uhc_sf_store_row); acc7: pen_sum, skate_sum, h_min, pen_n, skate_n, contact_n, above_n
+PROBE_API void uhc_surface_probe_store_row(const double* acc7, int n_vert, int has_next, int row_ok, int next_ok, double* out) {
+    UhcSfAcc a;
+    a.pen_sum = acc7[0], a.skate_sum = acc7[1], a.h_min = acc7[2];
+    a.pen_n = (int)acc7[3], a.skate_n = (int)acc7[4], a.contact_n = (int)acc7[5], a.above_n = (int)acc7[6];
+    uhc_sf_store_row(out, a, n_vert, has_next != 0, row_ok != 0, next_ok != 0);
+}
+
 // one vertex: world position (out[0:3]), height (out[3]) and the three predicates (out[4:7] as 0 / 1)
 PROBE_API void uhc_surface_probe_vertex(const double* pos3, const double* quat4, const double* v3, double radius, double floor_z, double* out) {
     const UhcSfPose P = uhc_sf_pose(pos3, quat4);

@@ -15,7 +15,9 @@ CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
 STEP_UNITS = [s for s in g.HIP_SOURCES if s.startswith("uhc_k_")] + ["uhc_batch_kernels.hip"]  # the units that include uhc_physics_impl.h
 ENV_UNITS = ["uhc_env.hip", "uhc_env_capi.cpp", "uhc_expert.hip"]
 STEP_HEADERS = ["uhc_physics_impl.h", "uhc_mpr.h", "uhc_primal.h", "uhc_device.h", "uhc_step_words.h", "uhc_launch.h"]
-TIER4_UNITS = ["uhc_k_big.hip", "uhc_k_big_fwd.hip", "uhc_k_huge_q.hip"]  # (#define UHC_WITH_TIER4: tier 4 is compiled into the large tier's kernels only)
+POST_UNITS = ["uhc_expert.hip", "uhc_eval.hip", "uhc_smpl.hip", "uhc_surface.hip", "uhc_smpl_mesh.hip", "uhc_rollout.hip", "uhc_live.hip"]  # the device-side post-processing
+POST_HEADERS = ["uhc_seq.h", "uhc_api_check.h"]  # their shared sequence rules and host-side checks
+TIER4_UNITS =["uhc_k_big.hip", "uhc_k_big_fwd.hip", "uhc_k_huge_q.hip"]  # (#define UHC_WITH_TIER4: tier 4 is compiled into the large tier's kernels only)
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +51,19 @@ def test_env_layer_depends_on_no_step_header(deps):
     for u in ENV_UNITS:
         assert names[u] & set(STEP_HEADERS) == set(), (u, names[u])
         assert "uhc_device_env.h" in names[u]
-    assert names["uhc_rollout.hip"] == set()
+    assert names["uhc_rollout.hip"] == {"uhc_api_check.h"}
+
+
+def test_post_processing_units_and_step_units_stay_apart(deps):
+    # the post-processing units read no step header (an edit of the step does not rebuild them), and no step unit reads the two headers those units share
+    # (an edit of uhc_seq.h or uhc_api_check.h rebuilds no step-kernel object)
+    names, _ = deps
+    for u in POST_UNITS:
+        assert names[u] & set(STEP_HEADERS) == set(), (u, names[u])
+        # (uhc_rollout.hip has no sequences, uhc_live.hip -- its model index clamped by the same rule -- no C entry of its own)
+        assert ("uhc_seq.h" in names[u]) == (u != "uhc_rollout.hip") and ("uhc_api_check.h" in names[u]) == (u != "uhc_live.hip"), (u, names[u])
+    for u in STEP_UNITS:
+        assert names[u] & set(POST_HEADERS) == set(), (u, names[u])
 
 
 def test_every_dependency_lies_inside_the_repository(deps):

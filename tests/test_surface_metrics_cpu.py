@@ -25,7 +25,7 @@ def build_probe():
     os.makedirs(out_dir, exist_ok=True)
     so = os.path.join(out_dir, "surface_metrics_probe.so")
     src = os.path.join(ROOT, "tests", "surface_metrics_probe.cpp")
-    deps = [src, os.path.join(CSRC, "uhc_surface_math.h")]
+    deps = [src, os.path.join(CSRC, "uhc_surface_math.h"), os.path.join(CSRC, "uhc_seq.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         tmp = so + f".{os.getpid()}.tmp"
         # (-ffp-contract=off: products and sums rounded separately, as the device unit is compiled)
@@ -114,6 +114,25 @@ def test_a_vertex_exactly_on_the_floor_counts_for_skate_and_contact_not_for_pene
         from uhc_amd.smpllib.smpl_eval import hull_vertices
         w = hull_vertices(SC.tables(c), c["pos"], c["quat"])  # the one vertex touches the floor in every row: its skate is how far it slides
         np.testing.assert_allclose(rows[:4, 1], np.linalg.norm(w[1:, 0, :2] - w[:-1, 0, :2], axis=1) * 1000, atol=ATOL, rtol=0)
+
+
+@pytest.mark.parametrize("has_next", [False, True])
+@pytest.mark.parametrize("row_ok,next_ok", [(True, True), (True, False), (False, True), (False, False)])
+def test_store_row_writes_nan_for_a_bad_row_and_leaves_the_skate_of_a_last_row_alone(probe, has_next, row_ok, next_ok):
+    # uhc_sf_store_row is the function uhc_surface_rows_kernel, uhc_smpl_mesh_kernel and the host loop all finish a row with
+    V = 7
+    for acc in ([-0.06, 0.012, -0.03, 3, 2, 4, 3], [0.0, 0.0, 0.25, 0, 0, 0, V]):  # some vertices below the floor and sliding; every vertex above it
+        out = np.full(4, SC.SENTINEL)
+        probe.uhc_surface_probe_store_row(_ptr(np.array(acc, dtype=np.float64)), C.c_int(V), C.c_int(has_next), C.c_int(row_ok), C.c_int(next_ok), _ptr(out))
+        pen_sum, skate_sum, h_min, pen_n, skate_n, contact_n, above_n = acc
+        want = [-(pen_sum / pen_n) * 1000.0 if pen_n else 0.0, skate_sum / skate_n * 1000.0 if skate_n else 0.0, h_min * 1000.0 if above_n == V else 0.0, float(contact_n)]
+        if not row_ok:
+            want = [np.nan] * 4
+        elif not next_ok:
+            want[1] = np.nan
+        if not has_next:
+            want[1] = SC.SENTINEL  # the slot is not touched: no row r + 1, no skate
+        np.testing.assert_array_equal(out, want)  # (NaN equals NaN here; the finite values are the same expressions: exact)
 
 
 def test_host_functions_and_probe_reproduce_the_values_recorded_from_the_reference(probe):

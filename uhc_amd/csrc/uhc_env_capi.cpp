@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/uhc_amd.h"
+#include "uhc_api_check.h"  // uhc_internal_set_error, HIP_OK
 #include "uhc_device_env.h"
 #include "uhc_expert_math.h"  // XfTree: the kinematic tree uhc_env_live_push hands its kernel
 
@@ -27,14 +28,7 @@ extern "C" hipError_t uhc_launch_env_assign(const EnvArgs* E, const int* env_ids
 // accessors implemented in uhc_capi.cpp
 extern "C" int uhc_internal_batch_info(UhcBatch* b, int* n_env, int* nq, int* nv, int* nu, int* nbody, int* action_dim, int* vf_dim,
                                        double* dt, double* base_rot_inv, void** stream, int** reset_mask);
-extern "C" int uhc_internal_set_error(const char* msg);
 extern "C" int uhc_internal_trailing_free(UhcBatch* b);
-
-#define HIP_OK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) return uhc_internal_set_error((std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); \
-    } while (0)
 
 struct UhcEnv {
     UhcBatch* b = nullptr;

@@ -1,4 +1,4 @@
-// Evaluation on the device: uhc_eval_record, uhc_eval_metrics (include/uhc_amd.h).
+// Evaluation on the device: uhc_eval_record, uhc_eval_record_pose, uhc_eval_metrics (include/uhc_amd.h).
 //
 // An evaluation episode (AgentCopycat.eval_seqs; reference: uhc/agents/agent_copycat.py:438-494) reads out, per control step and env, the humanoid's qpos, its
 // joint positions and the expert frame it is compared with, and scores the trajectory at the end (uhc_amd/smpllib/smpl_eval.py).  Both halves are kernels here,
@@ -6,33 +6,31 @@
 //
 //   uhc_eval_record_kernel   one wave per env, four envs per workgroup.  Every lane reads the env's control words (alive, rows, done); the lanes copy the
 //                            nqh + 72 doubles of the row; lane 0 writes the counters LAST (its stores depend on the words the whole wave loaded with it).
+//   uhc_eval_record_pose_kernel  the same mapping: the 72 + 96 doubles (xpos / xquat of bodies 1 .. 24) of the row uhc_eval_record is about to append, for the
+//                            contact quality (uhc_surface.hip).  It reads the row counter and leaves it to uhc_eval_record, which is enqueued behind it on the
+//                            same stream; which env takes a snapshot, and into which row, is ev_snapshot_row for both.
 //   uhc_eval_rows_kernel     one wave per TWO rows (lanes 0 .. 31 the even one, 32 .. 63 the odd one), four waves per workgroup; within a half lane = joint.
 //                            The sums over the 24 joints are xor butterflies inside the half (16, 8, 4, 2, 1: every lane ends with the same bits, in an
 //                            order fixed by the lane numbers alone); the 3 x 3 SVD of the Procrustes term is computed by every lane of the half alike.
 //                            The arithmetic between the sums is uhc_eval_metrics.h, which the CPU test compiles for the host.
 //   uhc_eval_means_kernel    one thread per (env, metric): the mean over the env's rows in row order.
-// No floating-point atomics anywhere; the two counters that are added to (d_overflow, d_bad) are integers.
+// No floating-point atomics anywhere; the two counters that are added to (d_overflow, d_bad) are integers.  No row counter, whatever it holds, sends a read or
+// a write outside the arrays (uhc_seq.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/uhc_amd.h"
+#include "uhc_api_check.h"
 #include "uhc_device_env.h"
-
-#include <string>
 
 #pragma clang fp contract(off)
 #include "uhc_eval_metrics.h"
+#include "uhc_seq.h"
 
 #define EV_NBODY 24
 #define EV_NJ3 (3 * EV_NBODY)
-#define EV_WAVES 4  // waves per workgroup
-
-extern "C" int uhc_internal_set_error(const char* msg);
-#define HIP_OK(expr)                                                                                                          \
-    do {                                                                                                                      \
-        hipError_t e__ = (expr);                                                                                              \
-        if (e__ != hipSuccess) return uhc_internal_set_error((std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); \
-    } while (0)
+#define EV_POSE_ROW (7 * EV_NBODY)  // a pose record's row: [24][3] positions, then [24][4] quaternions
+#define EV_WAVES 4                  // waves per workgroup
 
 // ------------------------------------------------------------------ the record
 struct RecordArgs {
@@ -51,6 +49,17 @@ struct RecordArgs {
     int *tele, *overflow;
 };
 
+// The snapshot rule of both record kernels, which must agree row for row: an env that is alive takes a snapshot before every step (phase 0), and once more (same
+// t) after the step that ended its episode (phase 1, done).  -> the row of the env's record it goes to; EV_NO_ROOM when the counter is outside 0 .. row_cap - 1
+// (nothing is written); EV_NO_SNAPSHOT when the env takes none.  done is read in phase 1 only, the counter only for a snapshot.
+enum { EV_NO_SNAPSHOT = -1, EV_NO_ROOM = -2 };
+__device__ __forceinline__ int ev_snapshot_row(int phase, const int* alive, const int* done, const int* rows, int row_cap, int e) {
+    if (alive[e] == 0) return EV_NO_SNAPSHOT;
+    if (!(phase == 0 || done[e] != 0)) return EV_NO_SNAPSHOT;
+    const int r = rows[e];
+    return r < 0 || r >= row_cap ? EV_NO_ROOM : r;
+}
+
 __global__ void __launch_bounds__(64 * EV_WAVES) uhc_eval_record_kernel(const RecordArgs A) {
     const int lane = threadIdx.x & 63, e = blockIdx.x * EV_WAVES + (threadIdx.x >> 6);
     if (e >= A.n_env) return;
@@ -59,10 +68,10 @@ __global__ void __launch_bounds__(64 * EV_WAVES) uhc_eval_record_kernel(const Re
         if (A.phase == 1 && lane == 0) A.tele[e] = 0;
         return;
     }
-    const int rows = A.rows[e];
     const bool done = A.phase == 1 && A.done[e] != 0;
-    if (A.phase == 0 || done) {  // a snapshot: before every step, and once more (same t) after the step that ended the episode
-        if (rows < 0 || rows >= A.row_cap) {
+    const int rows = ev_snapshot_row(A.phase, A.alive, A.done, A.rows, A.row_cap, e);
+    if (rows != EV_NO_SNAPSHOT) {
+        if (rows == EV_NO_ROOM) {
             if (lane == 0) atomicAdd(A.overflow, 1);  // (an integer count; nothing is written)
         } else {
             const size_t row = (size_t)e * A.row_cap + rows;
@@ -98,6 +107,26 @@ __global__ void __launch_bounds__(64 * EV_WAVES) uhc_eval_record_kernel(const Re
     }
 }
 
+// ------------------------------------------------------------------ the pose record
+struct RecordPoseArgs {
+    int phase, n_env, nbody, row_cap;
+    const double *xpos, *xquat;  // [n_env][nbody][3], [n_env][nbody][4] (body 0 = the world)
+    const int *done, *alive, *rows;
+    double* pose;  // [n_env][row_cap][168]
+};
+
+__global__ void __launch_bounds__(64 * EV_WAVES) uhc_eval_record_pose_kernel(const RecordPoseArgs A) {
+    const int lane = threadIdx.x & 63, e = blockIdx.x * EV_WAVES + (threadIdx.x >> 6);
+    if (e >= A.n_env) return;
+    const int rows = ev_snapshot_row(A.phase, A.alive, A.done, A.rows, A.row_cap, e);
+    if (rows < 0) return;  // (no snapshot, or no room: uhc_eval_record counts the overflow)
+    double* out = A.pose + ((size_t)e * A.row_cap + rows) * EV_POSE_ROW;
+    const double* x = A.xpos + (size_t)e * A.nbody * 3 + 3;  // bodies 1 .. 24
+    const double* q = A.xquat + (size_t)e * A.nbody * 4 + 4;
+    for (int j = lane; j < 3 * EV_NBODY; j += 64) out[j] = x[j];
+    for (int j = lane; j < 4 * EV_NBODY; j += 64) out[3 * EV_NBODY + j] = q[j];
+}
+
 // ------------------------------------------------------------------ the metrics
 struct MetricArgs {
     int n_env, nqh, row_cap;
@@ -110,18 +139,6 @@ struct MetricArgs {
     int* bad;
 };
 
-__device__ __forceinline__ int rows_of(const MetricArgs& A, int e) {  // whatever the counter holds, the rows read lie inside the arrays
-    const int r = A.rows[e];
-    return r < 0 ? 0 : (r > A.row_cap ? A.row_cap : r);
-}
-
-// the sum over the 32 lanes of the caller's half: the same bits in every lane
-__device__ __forceinline__ double half_sum(double v) {
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 __global__ void __launch_bounds__(64 * EV_WAVES) uhc_eval_rows_kernel(const MetricArgs A) {
     const int lane = threadIdx.x & 63, joint = lane & 31;
     const long long R = ((long long)blockIdx.x * EV_WAVES + (threadIdx.x >> 6)) * 2 + (lane >> 5);
@@ -129,7 +146,7 @@ __global__ void __launch_bounds__(64 * EV_WAVES) uhc_eval_rows_kernel(const Metr
     // (no lane leaves before the last butterfly: a half without a row computes on zeros and stores nothing)
     const bool in_grid = R < n_rows_all;
     const int e = in_grid ? (int)(R / A.row_cap) : 0, r = in_grid ? (int)(R % A.row_cap) : 0;
-    const int T = rows_of(A, e);
+    const int T = uhc_seq_rows(A.rows[e], A.row_cap);
     const bool valid = in_grid && r < T;
     const int n_next = !valid ? 0 : (T - 1 - r < 2 ? T - 1 - r : 2);
     const bool has_joint = joint < EV_NBODY;
@@ -163,23 +180,23 @@ __global__ void __launch_bounds__(64 * EV_WAVES) uhc_eval_rows_kernel(const Metr
     const UhcEmV3 gr = {__shfl(g[0].x, root_lane), __shfl(g[0].y, root_lane), __shfl(g[0].z, root_lane)};
     UhcEmJoint J = uhc_em_joint_norms(p, g, pr, gr);
     if (!has_joint) J.g = J.m = J.vel = J.acc = 0.0, J.p0 = J.g0 = {0.0, 0.0, 0.0};
-    const double sg = half_sum(J.g), sm = half_sum(J.m), sv = half_sum(J.vel), sa = half_sum(J.acc);
-    const UhcEmV3 muX = {half_sum(J.g0.x) / EV_NBODY, half_sum(J.g0.y) / EV_NBODY, half_sum(J.g0.z) / EV_NBODY};
-    const UhcEmV3 muY = {half_sum(J.p0.x) / EV_NBODY, half_sum(J.p0.y) / EV_NBODY, half_sum(J.p0.z) / EV_NBODY};
+    const double sg = uhc_xor_sum<16>(J.g), sm = uhc_xor_sum<16>(J.m), sv = uhc_xor_sum<16>(J.vel), sa = uhc_xor_sum<16>(J.acc);
+    const UhcEmV3 muX = {uhc_xor_sum<16>(J.g0.x) / EV_NBODY, uhc_xor_sum<16>(J.g0.y) / EV_NBODY, uhc_xor_sum<16>(J.g0.z) / EV_NBODY};
+    const UhcEmV3 muY = {uhc_xor_sum<16>(J.p0.x) / EV_NBODY, uhc_xor_sum<16>(J.p0.y) / EV_NBODY, uhc_xor_sum<16>(J.p0.z) / EV_NBODY};
     UhcEmV3 x0 = {J.g0.x - muX.x, J.g0.y - muX.y, J.g0.z - muX.z}, y0 = {J.p0.x - muY.x, J.p0.y - muY.y, J.p0.z - muY.z};
     if (!has_joint) x0 = y0 = {0.0, 0.0, 0.0};
-    const double nX = sqrt(half_sum(x0.x * x0.x + x0.y * x0.y + x0.z * x0.z)), nY = sqrt(half_sum(y0.x * y0.x + y0.y * y0.y + y0.z * y0.z));
+    const double nX = sqrt(uhc_xor_sum<16>(x0.x * x0.x + x0.y * x0.y + x0.z * x0.z)), nY = sqrt(uhc_xor_sum<16>(y0.x * y0.x + y0.y * y0.y + y0.z * y0.z));
     const double xn[3] = {x0.x / nX, x0.y / nX, x0.z / nX}, yn[3] = {y0.x / nY, y0.y / nY, y0.z / nY};
     double H[9];
 #pragma unroll
     for (int a = 0; a < 3; a++)
 #pragma unroll
-        for (int b = 0; b < 3; b++) H[3 * a + b] = half_sum(has_joint ? xn[a] * yn[b] : 0.0);
+        for (int b = 0; b < 3; b++) H[3 * a + b] = uhc_xor_sum<16>(has_joint ? xn[a] * yn[b] : 0.0);
     const UhcEmAlign Al = uhc_em_procrustes(H, nX, nY, muX, muY);
-    const double sp = half_sum(has_joint ? uhc_em_aligned_err(Al, J.p0, J.g0) : 0.0);
+    const double sp = uhc_xor_sum<16>(has_joint ? uhc_em_aligned_err(Al, J.p0, J.g0) : 0.0);
 
     if (valid && joint == 0) {
-        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        const double nan = uhc_nan();
         double* out = A.row_metrics + ((size_t)e * A.row_cap + r) * UHC_EM_NMETRIC;
         double root = nan;
         if (ok[0]) root = uhc_em_root_err(A.pred_qpos + ((size_t)e * A.row_cap + r) * A.nqh, A.frames + (size_t)f[0] * UHC_FRAME_STRIDE + UHC_FR_QPOS) / T * 1000.0;
@@ -196,18 +213,12 @@ __global__ void __launch_bounds__(256) uhc_eval_means_kernel(const MetricArgs A)
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= A.n_env * UHC_EM_NMETRIC) return;
     const int e = idx / UHC_EM_NMETRIC, k = idx % UHC_EM_NMETRIC;
-    const int T = rows_of(A, e);
-    int n = T - (k == UHC_EM_VEL_DIST ? 1 : (k == UHC_EM_ACCEL_DIST ? 2 : 0));  // numpy's lengths: T, T - 1 for the velocity, T - 2 for the acceleration
-    n = n < 0 ? 0 : n;
-    double s = 0.0;
-    for (int r = 0; r < n; r++) s += A.row_metrics[((size_t)e * A.row_cap + r) * UHC_EM_NMETRIC + k];
-    A.clip_means[idx] = n > 0 ? s / n : __longlong_as_double(0x7ff8000000000000LL);  // np.mean of an empty array
+    const int T = uhc_seq_rows(A.rows[e], A.row_cap);
+    const int n = T - (k == UHC_EM_VEL_DIST ? 1 : (k == UHC_EM_ACCEL_DIST ? 2 : 0));  // numpy's lengths: T, T - 1 for the velocity, T - 2 for the acceleration
+    A.clip_means[idx] = uhc_seq_mean(A.row_metrics, UHC_EM_NMETRIC, k, (long long)e * A.row_cap, n);
 }
 
 // ------------------------------------------------------------------ C-ABI (include/uhc_amd.h)
-#define REFUSE(fn, cond, what) \
-    if (cond) return uhc_internal_set_error(fn ": " what)
-
 extern "C" int32_t uhc_eval_record(void* stream, int32_t phase, int32_t n_env, int32_t n_body, int32_t nq, int32_t nqh, int32_t nbody, int32_t row_cap,
                                    int32_t t, int32_t fail_safe, const double* d_qpos, const double* d_xpos, const int64_t* d_clip0, const int32_t* d_len,
                                    const int32_t* d_done, const double* d_reward, const double* d_percent_in, int32_t* d_alive, int32_t* d_rows,
@@ -250,6 +261,27 @@ extern "C" int32_t uhc_eval_record(void* stream, int32_t phase, int32_t n_env, i
     return 0;
 }
 
+extern "C" int32_t uhc_eval_record_pose(void* stream, int32_t phase, int32_t n_env, int32_t nbody, int32_t row_cap, const double* d_xpos, const double* d_xquat,
+                                        const int32_t* d_done, const int32_t* d_alive, const int32_t* d_rows, double* d_pose) {
+    REFUSE("uhc_eval_record_pose", phase != 0 && phase != 1, "phase must be 0 (before the step) or 1 (after it)");
+    REFUSE("uhc_eval_record_pose", n_env < 0, "n_env < 0");
+    REFUSE("uhc_eval_record_pose", nbody < EV_NBODY + 1, "nbody must be at least 25 (the world body comes first, a row holds 24 poses)");
+    REFUSE("uhc_eval_record_pose", row_cap <= 0, "row_cap <= 0");
+    REFUSE("uhc_eval_record_pose", !d_xpos, "d_xpos is NULL");
+    REFUSE("uhc_eval_record_pose", !d_xquat, "d_xquat is NULL");
+    REFUSE("uhc_eval_record_pose", phase == 1 && !d_done, "d_done is NULL");
+    REFUSE("uhc_eval_record_pose", !d_alive, "d_alive is NULL");
+    REFUSE("uhc_eval_record_pose", !d_rows, "d_rows is NULL");
+    REFUSE("uhc_eval_record_pose", !d_pose, "d_pose is NULL");
+    if (n_env == 0) return 0;
+    RecordPoseArgs A = {};
+    A.phase = phase, A.n_env = n_env, A.nbody = nbody, A.row_cap = row_cap, A.xpos = d_xpos, A.xquat = d_xquat, A.done = d_done, A.alive = d_alive, A.rows = d_rows;
+    A.pose = d_pose;
+    hipLaunchKernelGGL(uhc_eval_record_pose_kernel, dim3((unsigned)((n_env + EV_WAVES - 1) / EV_WAVES)), dim3(64 * EV_WAVES), 0, (hipStream_t)stream, A);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int32_t uhc_eval_metrics(void* stream, int32_t n_env, int32_t n_body, int32_t nqh, int32_t row_cap, const int32_t* d_rows,
                                     const double* d_pred_qpos, const double* d_pred_jpos, const int64_t* d_gt_frame, const double* d_frames,
                                     int64_t n_frames, double* d_row_metrics, double* d_clip_means, int32_t* d_bad, int32_t* h_bad) {
@@ -267,7 +299,7 @@ extern "C" int32_t uhc_eval_metrics(void* stream, int32_t n_env, int32_t n_body,
     REFUSE("uhc_eval_metrics", !d_clip_means, "d_clip_means is NULL");
     REFUSE("uhc_eval_metrics", !d_bad, "d_bad is NULL");
     const long long blocks = ((long long)n_env * row_cap + 2 * EV_WAVES - 1) / (2 * EV_WAVES);
-    REFUSE("uhc_eval_metrics", blocks > 0x7fffffffLL || (long long)n_env * UHC_EM_NMETRIC > 0x7fffffffLL, "n_env x row_cap is beyond one launch");
+    REFUSE("uhc_eval_metrics", !uhc_launch_fits(blocks) || !uhc_launch_fits((long long)n_env * UHC_EM_NMETRIC), "n_env x row_cap is beyond one launch");
     if (n_env == 0) {
         if (h_bad) *h_bad = 0;
         return 0;
@@ -281,9 +313,5 @@ extern "C" int32_t uhc_eval_metrics(void* stream, int32_t n_env, int32_t n_body,
     HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(uhc_eval_means_kernel, dim3((unsigned)((n_env * UHC_EM_NMETRIC + 255) / 256)), dim3(256), 0, s, A);
     HIP_OK(hipGetLastError());
-    if (h_bad) {  // the caller wants the count now: the one place that waits for the stream
-        HIP_OK(hipMemcpyAsync(h_bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-    }
-    return 0;
+    return uhc_return_bad(h_bad, d_bad, s);
 }

@@ -9,7 +9,7 @@
 //   lanes b, 32 + b (b < 24)  turn body b's three Euler angles into the joint quaternion for BOTH frames of the half's difference pair (a, b): the pair is
 //                   (t - 1, t) for frame t >= 1 of a clip and (0, 1) for its frame 0 -- the cat((qvel[0:1], qvel)) rule --; a clip of ONE frame has
 //                   no pair: its qvel and bangvel are zero (the host path cannot compute such a clip at all).  The frame's clip -- and with it the pair
-//                   and the body shape -- is the lane's own binary search in d_clip_start, so the two halves may sit in different clips.
+//                   and the body shape -- is the lane's own binary search in d_clip_start (uhc_seq.h: uhc_clip_of), so the two halves may sit in different clips.
 //                   Then the finite differences, and the tree level by level: a body reads its parent's world pose from the parent's lane of its
 //                   half (ds_bpermute), depth <= 23 rounds, 8 on the SMPL tree.  Every field goes into the half's record in LDS.
 //   all 64 lanes    copy the wave's two records out, 16 B per lane to consecutive addresses (2 x 292 x 16 B: 9.1 wave-wide stores per wave).
@@ -22,21 +22,14 @@
 #include <stdint.h>
 
 #include "../../include/uhc_amd.h"
+#include "uhc_api_check.h"
 #include "uhc_device_env.h"
 #include "uhc_expert_math.h"  // the record of one pair of rows, shared with uhc_live.hip
-
-#include <string>
+#include "uhc_seq.h"
 
 #pragma clang fp contract(off)
 
 #define XF_WAVES 4  // waves per workgroup: eight frames
-
-extern "C" int uhc_internal_set_error(const char* msg);
-#define HIP_OK(expr)                                                                                                          \
-    do {                                                                                                                      \
-        hipError_t e__ = (expr);                                                                                              \
-        if (e__ != hipSuccess) return uhc_internal_set_error((std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); \
-    } while (0)
 
 struct ExpertArgs {
     const double* qpos;         // [n_frames][76]
@@ -61,21 +54,14 @@ __global__ void __launch_bounds__(64 * XF_WAVES) uhc_expert_frames_kernel(const 
         const bool valid = f0 + half < A.n_frames;     // (the bank's last frame may have no partner: that half computes its neighbour's frame along and stores nothing)
         const long long f = valid ? f0 + half : f0;
         double* rec = rec_s[2 * wave + half];
-        // ---- the frame's clip: the last clip whose start is <= f (the kernel's own lookup)
-        int lo = 0, hi = A.n_clips - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if ((long long)A.clip_start[mid] <= f) lo = mid;
-            else hi = mid - 1;
-        }
+        const int lo = uhc_clip_of(A.clip_start, A.n_clips, f);  // the frame's clip
         const long long s = A.clip_start[lo];
         const long long e = lo + 1 < A.n_clips ? (long long)A.clip_start[lo + 1] : A.n_frames;
         // (a table that is not ascending cannot send a read outside [0, n_frames): such a frame is treated as a clip of its own)
         const bool paired = s >= 0 && s <= f && f < e && e <= A.n_frames && e - s >= 2;
         // the difference pair (a, b): (t - 1, t) for frame t >= 1 of a clip, (0, 1) for its frame 0; a clip of one frame has none
         const long long fa = paired ? (f > s ? f - 1 : s) : f, fb = paired ? fa + 1 : f;
-        int m = A.clip_model ? A.clip_model[lo] : 0;
-        m = m < 0 || m >= A.n_models ? 0 : m;
+        const int m = uhc_seq_model(A.clip_model, lo, A.n_models);
 
         // the record of the pair, in LDS (uhc_expert_math.h); frame 0 of a clip (and an unpaired frame) IS a, every other frame is b
         xf_half_record(A.tree, A.dt, A.qpos + (size_t)fa * XF_NQ, A.qpos + (size_t)fb * XF_NQ, f == fa, paired, A.root_record ? A.root_record + (size_t)f * 4 : nullptr,
@@ -96,23 +82,23 @@ extern "C" int32_t uhc_expert_frames(void* stream, int32_t n_body, const int32_t
                                      const double* d_body_ipos, int32_t n_models, const double* d_qpos, int64_t n_frames, const int32_t* d_clip_start,
                                      const int32_t* d_clip_model, int32_t n_clips, const double* d_root_quat_record, double dt, double* d_frames) {
     // every check comes before the first HIP call
-    if (n_body != XF_NBODY) return uhc_internal_set_error("uhc_expert_frames: n_body must be 24 (UHC_FRAME_STRIDE is a 24-body layout)");
-    if (!h_parent) return uhc_internal_set_error("uhc_expert_frames: h_parent is NULL");
-    if (!h_ee_body) return uhc_internal_set_error("uhc_expert_frames: h_ee_body is NULL");
-    if (!d_body_pos) return uhc_internal_set_error("uhc_expert_frames: d_body_pos is NULL");
-    if (!d_body_ipos) return uhc_internal_set_error("uhc_expert_frames: d_body_ipos is NULL");
-    if (!d_qpos) return uhc_internal_set_error("uhc_expert_frames: d_qpos is NULL");
-    if (!d_clip_start) return uhc_internal_set_error("uhc_expert_frames: d_clip_start is NULL");
-    if (!d_frames) return uhc_internal_set_error("uhc_expert_frames: d_frames is NULL");
-    if (n_frames < 0) return uhc_internal_set_error("uhc_expert_frames: n_frames < 0");
-    if (n_clips <= 0) return uhc_internal_set_error("uhc_expert_frames: n_clips <= 0");
-    if (n_models <= 0) return uhc_internal_set_error("uhc_expert_frames: n_models <= 0");
-    if (!(dt > 0.0)) return uhc_internal_set_error("uhc_expert_frames: dt <= 0");
+    REFUSE("uhc_expert_frames", n_body != XF_NBODY, "n_body must be 24 (UHC_FRAME_STRIDE is a 24-body layout)");
+    REFUSE("uhc_expert_frames", !h_parent, "h_parent is NULL");
+    REFUSE("uhc_expert_frames", !h_ee_body, "h_ee_body is NULL");
+    REFUSE("uhc_expert_frames", !d_body_pos, "d_body_pos is NULL");
+    REFUSE("uhc_expert_frames", !d_body_ipos, "d_body_ipos is NULL");
+    REFUSE("uhc_expert_frames", !d_qpos, "d_qpos is NULL");
+    REFUSE("uhc_expert_frames", !d_clip_start, "d_clip_start is NULL");
+    REFUSE("uhc_expert_frames", !d_frames, "d_frames is NULL");
+    REFUSE("uhc_expert_frames", n_frames < 0, "n_frames < 0");
+    REFUSE("uhc_expert_frames", n_clips <= 0, "n_clips <= 0");
+    REFUSE("uhc_expert_frames", n_models <= 0, "n_models <= 0");
+    REFUSE("uhc_expert_frames", !(dt > 0.0), "dt <= 0");
     ExpertArgs A = {};
     const std::string bad = xf_tree_fill("uhc_expert_frames", h_parent, h_ee_body, &A.tree);
     if (!bad.empty()) return uhc_internal_set_error(bad.c_str());
     const long long blocks = ((long long)n_frames + 2 * XF_WAVES - 1) / (2 * XF_WAVES);
-    if (blocks > 0x7fffffffLL) return uhc_internal_set_error("uhc_expert_frames: n_frames is beyond one launch (2^34 frames)");
+    REFUSE("uhc_expert_frames", !uhc_launch_fits(blocks), "n_frames is beyond one launch (2^34 frames)");
     if (n_frames == 0) return 0;
     A.qpos = d_qpos, A.root_record = d_root_quat_record, A.clip_start = d_clip_start, A.clip_model = d_clip_model;
     A.body_pos = d_body_pos, A.body_ipos = d_body_ipos, A.frames = d_frames;

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "uhc_device_env.h"
+#include "uhc_seq.h"  // uhc_packed_byte
 
 #pragma clang fp contract(off)
 
@@ -57,11 +58,6 @@ struct Q4 {
 struct V3 {
     double x, y, z;
 };
-
-__device__ __forceinline__ int packed_byte(const unsigned long long (&w)[3], int i) {
-    const unsigned long long v = i < 8 ? w[0] : (i < 16 ? w[1] : w[2]);
-    return (int)((v >> (8 * (i & 7))) & 0xff);
-}
 
 // quaternion_multiply_batch (torch_utils.py)
 __device__ __forceinline__ Q4 qmul(const Q4& a, const Q4& b) {
@@ -162,7 +158,7 @@ __device__ __forceinline__ void xf_half_record(const XfTree& T, double dt, const
     if (!paired) bangvel = v0 = v1 = {0.0, 0.0, 0.0};
 
     // ---- forward_kinematics_batch, level by level: world pose of the parent from the parent's lane (of the same half)
-    const int par = packed_byte(T.parent, bi) - 1, dep = packed_byte(T.depth, bi);
+    const int par = uhc_packed_byte(T.parent, bi) - 1, dep = uhc_packed_byte(T.depth, bi);
     const int par_lane = (lane & 32) + (par < 0 ? 0 : par);
     const double* off = body_pos + (size_t)bi * 3;
     const double* ioff = body_ipos + (size_t)bi * 3;

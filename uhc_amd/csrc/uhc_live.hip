@@ -1,7 +1,7 @@
 // Live targets: one expert frame record per env and control step, appended to the env's own stream: uhc_env_live_push (include/uhc_amd.h).
 //
 // The per-env, per-step form of uhc_expert.hip: the same record (uhc_expert_math.h), from the pair (the env's previous row, the pushed row) instead of two
-// rows of a bank found by a binary search, written to slot `len` of the env's stream in the live bank [n_env][cap][UHC_FRAME_STRIDE], with the per-env
+// rows of a bank found by a binary search (the model index is brought into its range by the same rule, uhc_seq.h), written to slot `len` of the env's stream in the live bank [n_env][cap][UHC_FRAME_STRIDE], with the per-env
 // bookkeeping the env kernels read (e_len, e_start, clip_id, height_lb).  The entry points and the memory are uhc_env_capi.cpp's.
 //
 // Mapping: one wave per TWO rows (lanes 0 .. 31 the even one, lanes 32 .. 63 the odd one), four waves per workgroup; within a half, lane = body.  A half
@@ -22,6 +22,7 @@
 #include "uhc_device_env.h"
 #include "uhc_expert_math.h"
 #include "uhc_live_window.h"
+#include "uhc_seq.h"
 
 #pragma clang fp contract(off)
 
@@ -71,7 +72,7 @@ __global__ void __launch_bounds__(64 * LV_WAVES) uhc_live_push_kernel(const Live
             L = A.live_len[env];
             what = A.restart && A.restart[r] ? 1 : (L >= 1 && L < A.cap ? 2 : 3);
             m = what == 1 && A.model ? A.model[r] : (A.env_model ? A.env_model[env] : 0);
-            m = m < 0 || m >= A.n_models ? 0 : m;
+            m = uhc_seq_model(m, A.n_models);
         }
         // the pair: (previous row, row) of an append; a restart is a clip of one frame, and so is what a half computes along
         const bool append = what == 2;

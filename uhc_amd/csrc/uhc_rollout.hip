@@ -11,17 +11,9 @@
 #include <stdint.h>
 
 #include "../../include/uhc_amd.h"  // (declares the entry points below with default visibility: the library is built -fvisibility=hidden)
-
-#include <string>
+#include "uhc_api_check.h"
 
 #define WAVE 64
-
-extern "C" int uhc_internal_set_error(const char* msg);
-#define HIP_OK(expr)                                                                                                          \
-    do {                                                                                                                      \
-        hipError_t e__ = (expr);                                                                                              \
-        if (e__ != hipSuccess) return uhc_internal_set_error((std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); \
-    } while (0)
 
 // ------------------------------------------------------------------ policy output -> action, rollout buffers
 // One thread per (env, j): j < obs_dim copies the filtered state into the pass buffer, the rest forms the action.  The sample is
@@ -195,9 +187,10 @@ __global__ void __launch_bounds__(256) uhc_filter_apply_kernel(const double* __r
 extern "C" int32_t uhc_rollout_act(void* stream, int32_t n_env, int32_t T, const int64_t* d_t, int32_t obs_dim, int32_t act_dim, const double* d_state,
                                    const double* d_mean, const double* d_log_std, const double* d_noise, const double* d_mean_flags, double* d_states,
                                    double* d_actions, double* d_action) {
-    if (n_env <= 0 || T <= 0 || obs_dim < 0 || act_dim <= 0 || !d_t || !d_mean || !d_log_std || !d_noise || !d_mean_flags || !d_actions || !d_action ||
-        (obs_dim > 0 && (!d_state || !d_states)))
-        return uhc_internal_set_error("uhc_rollout_act: bad argument");
+    REFUSE("uhc_rollout_act",
+           n_env <= 0 || T <= 0 || obs_dim < 0 || act_dim <= 0 || !d_t || !d_mean || !d_log_std || !d_noise || !d_mean_flags || !d_actions || !d_action ||
+               (obs_dim > 0 && (!d_state || !d_states)),
+           "bad argument");
     const long long total = (long long)n_env * (obs_dim + act_dim);
     hipLaunchKernelGGL(uhc_rollout_act_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_env, T, (const long long*)d_t, obs_dim,
                        act_dim, d_state, d_mean, d_log_std, d_noise, d_mean_flags, d_states, d_actions, d_action);
@@ -209,9 +202,10 @@ extern "C" int32_t uhc_rollout_record(void* stream, int32_t n_env, int32_t T, co
                                       const int32_t* d_end, const double* d_end_reward, const double* d_parts, int32_t parts_stride, int32_t n_parts,
                                       double* d_rewards, double* d_dones, double* d_c_reward_sum, double* d_c_info_sum, const int32_t* d_redo,
                                       int64_t* d_redo_counts) {
-    if ((d_redo && !d_redo_counts) || n_env <= 0 || T <= 0 || !d_t || !d_reward || !d_done || !d_end || !d_end_reward || !d_rewards || !d_dones || !d_c_reward_sum || n_parts < 0 ||
-        n_parts > 8 || (n_parts > 0 && (!d_parts || !d_c_info_sum || parts_stride < n_parts)))
-        return uhc_internal_set_error("uhc_rollout_record: bad argument");
+    REFUSE("uhc_rollout_record",
+           (d_redo && !d_redo_counts) || n_env <= 0 || T <= 0 || !d_t || !d_reward || !d_done || !d_end || !d_end_reward || !d_rewards || !d_dones || !d_c_reward_sum ||
+               n_parts < 0 || n_parts > 8 || (n_parts > 0 && (!d_parts || !d_c_info_sum || parts_stride < n_parts)),
+           "bad argument");
     hipLaunchKernelGGL(uhc_rollout_record_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n_env, T, (const long long*)d_t, d_reward, d_done, d_end,
                        d_end_reward, d_parts, parts_stride, n_parts, d_rewards, d_dones, d_c_reward_sum, d_c_info_sum, d_redo, (long long*)d_redo_counts);
     HIP_OK(hipGetLastError());
@@ -225,7 +219,7 @@ extern "C" int64_t uhc_filter_scratch_doubles(int32_t n_rows, int32_t dim) {
 
 extern "C" int32_t uhc_filter_push(void* stream, const double* d_x, int32_t n_rows, int32_t dim, const int32_t* d_weights, double* d_n, double* d_mean,
                                    double* d_S, double* d_scratch) {
-    if (n_rows < 0 || dim <= 0 || !d_x || !d_n || !d_mean || !d_S || !d_scratch) return uhc_internal_set_error("uhc_filter_push: bad argument");
+    REFUSE("uhc_filter_push", n_rows < 0 || dim <= 0 || !d_x || !d_n || !d_mean || !d_S || !d_scratch, "bad argument");
     if (n_rows == 0) return 0;
     const int R = (n_rows + FP_ROWS_PER_BLOCK - 1) / FP_ROWS_PER_BLOCK;
     double* part = d_scratch;
@@ -240,7 +234,7 @@ extern "C" int32_t uhc_filter_push(void* stream, const double* d_x, int32_t n_ro
 
 extern "C" int32_t uhc_filter_apply(void* stream, const double* d_x, int32_t n_rows, int32_t dim, const double* d_n, const double* d_mean, const double* d_S,
                                     int32_t demean, int32_t destd, double clip, double* d_out, int64_t* d_t_inc) {
-    if (n_rows < 0 || dim <= 0 || !d_x || !d_n || !d_mean || !d_S || !d_out) return uhc_internal_set_error("uhc_filter_apply: bad argument");
+    REFUSE("uhc_filter_apply", n_rows < 0 || dim <= 0 || !d_x || !d_n || !d_mean || !d_S || !d_out, "bad argument");
     const long long total = (long long)n_rows * dim;
     const unsigned blocks = (unsigned)((total + 255) / 256);
     hipLaunchKernelGGL(uhc_filter_apply_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, (hipStream_t)stream, d_x, n_rows, dim, d_n, d_mean, d_S, demean,

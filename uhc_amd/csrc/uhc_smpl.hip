@@ -9,11 +9,11 @@
 //   lane (f, j)     reads joint j's 24 bytes -- a workgroup's lanes read one run of consecutive addresses --, forms the quaternion and from it the hinge triple
 //                   and / or the (w, x, y, z) quadruple in registers, and puts them into slot slot_of_joint[j] of the frame's row(s) in LDS.
 //   lane (f, 0)     also forms the root quaternion of the 76-wide row (through the rotation matrix: the branch rule that fixes its sign) and the root position:
-//                   trans + root_offset[model of the frame's clip]; the clip is the lane's own binary search in d_clip_start, as in uhc_expert.hip.
+//                   trans + root_offset[model of the frame's clip]; the clip is the lane's own binary search in d_clip_start (uhc_seq.h: uhc_clip_of).
 //   all lanes       copy the workgroup's rows out, 16 B per lane to consecutive addresses.  A workgroup starts at an even frame, so its rows start 16-byte
 //                   aligned (8 x 608 B, 8 x 792 B); an odd number of 99-wide rows (the bank's tail) ends in one 8-byte store.
 // No array is indexed at run time by a value read from memory: the slot table arrives packed in kernel-argument words (checked on the host to be a
-// permutation), a clip's model index is range-checked before it selects a root offset.  No atomics; no scratch.
+// permutation), a clip's model index is range-checked before it selects a root offset (uhc_seq.h).  No atomics; no scratch.
 //
 // Arithmetic: uhc_smpl_convert.h, scipy's formulas one for one, products and sums rounded separately (no FMA contraction), so that what differs from the
 // host path are the last bits of sqrt / sin / cos / atan2 / hypot alone.
@@ -21,21 +21,14 @@
 #include <stdint.h>
 
 #include "../../include/uhc_amd.h"
+#include "uhc_api_check.h"
+#include "uhc_seq.h"
 #include "uhc_smpl_convert.h"
-
-#include <string>
 
 #pragma clang fp contract(off)
 
 #define SC_FRAMES 8                        // frames per workgroup (even: see above)
 #define SC_THREADS (SC_FRAMES * UHC_SC_NJ)  // 192: three waves
-
-extern "C" int uhc_internal_set_error(const char* msg);
-#define HIP_OK(expr)                                                                                                          \
-    do {                                                                                                                      \
-        hipError_t e__ = (expr);                                                                                              \
-        if (e__ != hipSuccess) return uhc_internal_set_error((std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); \
-    } while (0)
 
 struct SmplArgs {
     const double* pose;         // [n_frames][72]
@@ -49,11 +42,6 @@ struct SmplArgs {
     int n_clips, n_models;
     unsigned long long slot[3];  // the model slot of SMPL joint j, one byte per joint
 };
-
-__device__ __forceinline__ int packed_byte(const unsigned long long (&w)[3], int i) {
-    const unsigned long long v = i < 8 ? w[0] : (i < 16 ? w[1] : w[2]);
-    return (int)((v >> (8 * (i & 7))) & 0xff);
-}
 
 // The body of both kernels that write qpos rows.  SIX = false: A.pose holds rotation vectors [n_frames][72] and A.trans the translations (uhc_smpl_qpos);
 // SIX = true: A.pose holds 6D rows [n_frames][147] = translation | 24 x (column 0, column 1), the joint's quaternion comes from uhc_sc_rot6d_quat and the
@@ -71,7 +59,7 @@ __device__ __forceinline__ void smpl_qpos_rows(const SmplArgs& A, double* row_s,
             const double* r = A.pose + (size_t)f * (3 * UHC_SC_NJ) + 3 * j;
             q = uhc_sc_rotvec_quat(r[0], r[1], r[2]);
         }
-        const int m = packed_byte(A.slot, j);  // (a permutation of 0 .. 23 with slot[0] = 0: checked before the launch)
+        const int m = uhc_packed_byte(A.slot, j);  // (a permutation of 0 .. 23 with slot[0] = 0: checked before the launch)
         double* row = row_s + fl * UHC_SC_NQ;
         double* qrow = quat_s + fl * UHC_SC_NQ_QUAT;
         if (A.qpos_quat) {
@@ -79,20 +67,9 @@ __device__ __forceinline__ void smpl_qpos_rows(const SmplArgs& A, double* row_s,
             o[0] = q.w, o[1] = q.x, o[2] = q.y, o[3] = q.z;
         }
         if (j == 0) {
-            // ---- the frame's clip: the last clip whose start is <= f; all it decides is which model's root offset the row gets
+            // ---- the frame's clip: all it decides is which model's root offset the row gets
             const double* off = nullptr;
-            if (A.root_offset) {
-                int lo = 0, hi = A.n_clips - 1;
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if ((long long)A.clip_start[mid] <= f) lo = mid;
-                    else hi = mid - 1;
-                }
-                // (lo stays inside the table whatever it holds: a table that is not ascending can name the wrong clip, never an address outside the arrays)
-                int mi = A.clip_model ? A.clip_model[lo] : 0;
-                mi = mi < 0 || mi >= A.n_models ? 0 : mi;
-                off = A.root_offset + (size_t)mi * 3;
-            }
+            if (A.root_offset) off = A.root_offset + (size_t)uhc_seq_model(A.clip_model, uhc_clip_of(A.clip_start, A.n_clips, f), A.n_models) * 3;
             const UhcScV3 p = uhc_sc_root_pos(SIX ? A.pose + (size_t)f * UHC_SC_N6D : (A.trans ? A.trans + (size_t)f * 3 : nullptr), off);
             if (A.qpos) {
                 double R[9];
@@ -171,7 +148,7 @@ struct PoseArgs {
 // the workgroup's live rows out of LDS (W doubles a row, one behind the other) to out (the workgroup's first row; 16-byte aligned), NaN for a bad row
 template <int W>
 __device__ __forceinline__ void pose_rows_out(double* out, const double* lds, const int* live_s, const int* bad_s, int nf, int tid) {
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double nan = uhc_nan();
     const int n = nf * W;
     for (int k = tid; 2 * k < n; k += SC_THREADS) {
         const int i0 = 2 * k, i1 = i0 + 1, r0 = i0 / W, r1 = i1 < n ? i1 / W : r0;
@@ -201,9 +178,7 @@ __global__ void __launch_bounds__(SC_THREADS) uhc_qpos_smpl_kernel(const PoseArg
             live = 1;
             if (A.seq_rows) {
                 const long long g = g0 + tid, s = g / A.row_cap;
-                int cnt = A.seq_rows[s];
-                cnt = cnt < 0 ? 0 : (cnt > A.row_cap ? A.row_cap : cnt);
-                live = (int)(g - s * A.row_cap) < cnt;
+                live = (int)(g - s * A.row_cap) < uhc_seq_rows(A.seq_rows[s], A.row_cap);
             }
         }
         live_s[tid] = live, bad_s[tid] = 0;
@@ -227,7 +202,7 @@ __global__ void __launch_bounds__(SC_THREADS) uhc_qpos_smpl_kernel(const PoseArg
     if (live_s[fl]) {
         const double* row = in_s + fl * SP_PITCH;
         UhcScQuat q;
-        const bool ok = uhc_sc_row_joint_quat(row, A.ball, j, packed_byte(A.slot, j), q);  // (the slot: a permutation of 0 .. 23 with slot[0] = 0, checked before the launch)
+        const bool ok = uhc_sc_row_joint_quat(row, A.ball, j, uhc_packed_byte(A.slot, j), q);  // (the slot: a permutation of 0 .. 23 with slot[0] = 0, checked before the launch)
         if (!ok) bad_s[fl] = 1;
         if (A.pose_aa) {
             const UhcScV3 r = uhc_sc_quat_rotvec(q);
@@ -242,9 +217,7 @@ __global__ void __launch_bounds__(SC_THREADS) uhc_qpos_smpl_kernel(const PoseArg
         if (j == 0) {
             double ox = 0.0, oy = 0.0, oz = 0.0;
             if (A.root_offset) {
-                int mi = A.seq_model ? A.seq_model[(g0 + fl) / A.row_cap] : 0;
-                mi = mi < 0 || mi >= A.n_models ? 0 : mi;
-                const double* off = A.root_offset + (size_t)mi * 3;
+                const double* off = A.root_offset + (size_t)uhc_seq_model(A.seq_model, (g0 + fl) / A.row_cap, A.n_models) * 3;
                 ox = off[0], oy = off[1], oz = off[2];
             }
             const double tx = row[0] - ox, ty = row[1] - oy, tz = row[2] - oz;
@@ -263,9 +236,6 @@ __global__ void __launch_bounds__(SC_THREADS) uhc_qpos_smpl_kernel(const PoseArg
 }
 
 // ------------------------------------------------------------------ C-ABI (include/uhc_amd.h)
-#define REFUSE(fn, cond, what) \
-    if (cond) return uhc_internal_set_error((std::string(fn) + ": " + (what)).c_str())
-
 // h_smpl_to_model [24] -> the model slot of every SMPL joint, one byte a joint; refused unless it is a permutation of 0 .. 23 that keeps the root at 0
 static int pack_slot_table(const char* fn, const int32_t* h_smpl_to_model, unsigned long long (&slot)[3]) {
     unsigned seen = 0;
@@ -300,7 +270,7 @@ static int smpl_qpos_launch(const char* fn, bool six, void* stream, int32_t n_jo
     SmplArgs A = {};
     if (pack_slot_table(fn, h_smpl_to_model, A.slot)) return 1;
     const long long blocks = ((long long)n_frames + SC_FRAMES - 1) / SC_FRAMES;
-    REFUSE(fn, blocks > 0x7fffffffLL, "n_frames is beyond one launch (2^34 frames)");
+    REFUSE(fn, !uhc_launch_fits(blocks), "n_frames is beyond one launch (2^34 frames)");
     if (n_frames == 0) return 0;
     A.pose = d_in, A.trans = d_trans, A.root_offset = d_root_offset, A.clip_start = d_clip_start, A.clip_model = d_clip_model;
     A.qpos = d_qpos, A.qpos_quat = d_qpos_quat;
@@ -350,7 +320,7 @@ extern "C" int32_t uhc_qpos_smpl(void* stream, int32_t n_joint, const int32_t* h
     PoseArgs A = {};
     if (pack_slot_table(fn, h_smpl_to_model, A.slot)) return 1;
     const long long n_rows = (long long)n_seq * row_cap, blocks = (n_rows + SC_FRAMES - 1) / SC_FRAMES;
-    REFUSE(fn, blocks > 0x7fffffffLL, "n_seq x row_cap is beyond one launch (2^34 rows)");
+    REFUSE(fn, !uhc_launch_fits(blocks), "n_seq x row_cap is beyond one launch (2^34 rows)");
     if (n_rows == 0) {
         if (h_bad) *h_bad = 0;
         return 0;
@@ -363,9 +333,5 @@ extern "C" int32_t uhc_qpos_smpl(void* stream, int32_t n_joint, const int32_t* h
     HIP_OK(hipMemsetAsync(d_bad, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(uhc_qpos_smpl_kernel, dim3((unsigned)blocks), dim3(SC_THREADS), 0, s, A);
     HIP_OK(hipGetLastError());
-    if (h_bad) {  // the caller wants the count now: the one place that waits for the stream
-        HIP_OK(hipMemcpyAsync(h_bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-    }
-    return 0;
+    return uhc_return_bad(h_bad, d_bad, s);
 }

@@ -14,30 +14,23 @@
 //                            barriers, so a load of the packed posedirs by one of them is in the cache for the other three: 64 rows (60 owned) per load.
 //   uhc_smpl_means_kernel    one thread per (sequence, metric): the mean over the sequence's rows in row order.
 // No floating-point atomics: a row's sums are per-lane partial sums in vertex-tile order and xor butterflies over the 16 lanes of its group.  No index, whatever
-// it holds, sends a read or a write outside the arrays (uhc_surface.hip's rules: row counts clamped, a sequence outside the rows skipped, a model index
-// outside the range reads as 0).
+// it holds, sends a read or a write outside the arrays (uhc_seq.h: row counts clamped, a sequence outside the rows skipped, a model index outside the range
+// reads as 0).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/uhc_amd.h"
+#include "uhc_api_check.h"
 
-#include <cmath>
-#include <string>
 #include <vector>
 
 #pragma clang fp contract(off)
+#include "uhc_seq.h"
 #include "uhc_smpl_mesh_math.h"
 #include "uhc_surface_math.h"
 
 #define SM_WAVES 4  // waves (row tiles) per workgroup
 #define SM_LDS_BYTES (sizeof(double) * SM_WAVES * UHC_SM_G_WAVE)
-
-extern "C" int uhc_internal_set_error(const char* msg);
-#define HIP_OK(expr)                                                                                                          \
-    do {                                                                                                                      \
-        hipError_t e__ = (expr);                                                                                              \
-        if (e__ != hipSuccess) return uhc_internal_set_error((std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); \
-    } while (0)
 
 struct UhcSmplMesh {
     int n_vert, n_vtiles, n_models, nw;
@@ -67,19 +60,10 @@ struct MeshArgs {
     int* bad;
 };
 
-__device__ __forceinline__ int sm_rows_of(const MeshArgs& A, int s) {  // whatever the entry holds, the rows read lie inside the arrays
-    const int r = A.seq_rows[s];
-    return r < 0 ? 0 : (r > A.row_cap ? A.row_cap : r);
-}
-// the sequence's first global row, or -1 when its T rows would leave 0 .. n_rows_total (the sequence is then skipped)
-__device__ __forceinline__ long long sm_start_of(const MeshArgs& A, int s, int T) {
-    const long long g = A.seq_start[s];
-    return g >= 0 && g <= A.n_rows_total - T ? g : -1;
-}
-__device__ __forceinline__ int sm_model_of(const MeshArgs& A, int s) {
-    const int m = A.seq_model ? A.seq_model[s] : 0;
-    return m >= 0 && m < A.n_models ? m : 0;
-}
+// sequence s as uhc_seq.h reads it: its rows, its first global row (-1: skipped), its model
+__device__ __forceinline__ int sm_rows_of(const MeshArgs& A, int s) { return uhc_seq_rows(A.seq_rows[s], A.row_cap); }
+__device__ __forceinline__ long long sm_start_of(const MeshArgs& A, int s, int T) { return uhc_seq_start(A.seq_start[s], T, A.n_rows_total); }
+__device__ __forceinline__ int sm_model_of(const MeshArgs& A, int s) { return uhc_seq_model(A.seq_model, s, A.n_models); }
 
 __global__ void __launch_bounds__(256) uhc_smpl_shape_kernel(const MeshArgs A) {
     const int vpad = UHC_SM_TILE * A.n_vtiles, per_seq = (vpad + 255) / 256;  // (the sequence rides in blockIdx.x: no 65 535 limit of a grid's y)
@@ -123,29 +107,10 @@ __global__ void __launch_bounds__(256) uhc_smpl_joints_kernel(const MeshArgs A) 
 
 typedef double sm_acc __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ double sm_group_sum(double v) {  // over the 16 lanes of a row group: every lane ends with the same bits
-#pragma unroll
-    for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ int sm_group_sum(int v) {
-#pragma unroll
-    for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ double sm_group_min(double v) {
-#pragma unroll
-    for (int m = 8; m >= 1; m >>= 1) {
-        const double o = __shfl_xor(v, m);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 __global__ void __launch_bounds__(64 * SM_WAVES) uhc_smpl_mesh_kernel(const MeshArgs A) {
     extern __shared__ __attribute__((aligned(16))) double sm_lds[];  // [SM_WAVES][UHC_SM_G_WAVE]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane >> 4;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double nan = uhc_nan();
     // (no wave leaves before the last barrier: one without rows loads nothing and stores nothing)
     const long long R = (long long)blockIdx.x * SM_WAVES + wave;
     const bool in_grid = R < (long long)A.n_seq * A.tiles_per_seq;
@@ -328,23 +293,15 @@ __global__ void __launch_bounds__(64 * SM_WAVES) uhc_smpl_mesh_kernel(const Mesh
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         UhcSfAcc w;
-        w.pen_sum = sm_group_sum(pen_sum[i]), w.skate_sum = sm_group_sum(skate_sum[i]);
-        const double zm = sm_group_min(z_min[i]);
+        // (over the 16 lanes of a row group: every lane ends with the same bits)
+        w.pen_sum = uhc_xor_sum<8>(pen_sum[i]), w.skate_sum = uhc_xor_sum<8>(skate_sum[i]);
+        const double zm = uhc_xor_min<8>(z_min[i]);
         w.h_min = zm - A.floor_z;  // (rounding is monotone: the minimum of the heights is the height of the lowest vertex)
-        w.pen_n = sm_group_sum(pen_n[i]), w.skate_n = sm_group_sum(skate_n[i]), w.contact_n = sm_group_sum(contact_n[i]), w.above_n = sm_group_sum(above_n[i]);
+        w.pen_n = uhc_xor_sum<8>(pen_n[i]), w.skate_n = uhc_xor_sum<8>(skate_n[i]), w.contact_n = uhc_xor_sum<8>(contact_n[i]), w.above_n = uhc_xor_sum<8>(above_n[i]);
         if (owned[i] && (lane & 15) == 0) {
             const size_t g = (size_t)(g0 + r0 + sm_cd_row(lane, i));
             if (A.zmin) A.zmin[g] = row_ok[i] ? zm : nan;
-            if (A.row_out) {
-                double* out = A.row_out + g * UHC_SF_NMETRIC;
-                if (row_ok[i]) {
-                    uhc_sf_finish(w, A.n_vert, has_next[i], out);
-                    if (has_next[i] && !next_ok[i]) out[UHC_SF_SKATE] = nan;
-                } else {
-                    out[UHC_SF_PEN] = out[UHC_SF_FLOAT] = out[UHC_SF_CONTACT] = nan;
-                    if (has_next[i]) out[UHC_SF_SKATE] = nan;
-                }
-            }
+            if (A.row_out) uhc_sf_store_row(A.row_out + g * UHC_SF_NMETRIC, w, A.n_vert, has_next[i], row_ok[i], next_ok[i]);
         }
     }
 }
@@ -356,30 +313,10 @@ __global__ void __launch_bounds__(256) uhc_smpl_means_kernel(const MeshArgs A) {
     const int T = sm_rows_of(A, s);
     const long long g0 = sm_start_of(A, s, T);
     if (g0 < 0) return;  // the sequence is skipped (and counted by uhc_smpl_shape_kernel): nothing of it is read or written
-    int n = T - (k == UHC_SF_SKATE ? 1 : 0);
-    n = n < 0 ? 0 : n;
-    double sum = 0.0;
-    for (int r = 0; r < n; r++) sum += A.row_out[(size_t)(g0 + r) * UHC_SF_NMETRIC + k];
-    A.seq_means[idx] = n > 0 ? sum / n : __longlong_as_double(0x7ff8000000000000LL);  // np.mean of an empty array
+    A.seq_means[idx] = uhc_seq_mean(A.row_out, UHC_SF_NMETRIC, k, g0, T - (k == UHC_SF_SKATE ? 1 : 0));  // (the skate: over the T - 1 pairs of rows)
 }
 
 // ------------------------------------------------------------------ C-ABI (include/uhc_amd.h)
-#define REFUSE(fn, cond, what) \
-    if (cond) return uhc_internal_set_error(fn ": " what)
-
-static bool all_finite(const double* p, size_t n) {
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-
-template <class T>
-static hipError_t upload(T** dst, const T* src, size_t n) {
-    hipError_t e = hipMalloc((void**)dst, sizeof(T) * n);
-    if (e == hipSuccess) e = hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice);
-    return e;
-}
-
 extern "C" int32_t uhc_smpl_mesh_create(int32_t n_vert, int32_t n_models, const double* h_v_template, const double* h_shapedirs, const double* h_posedirs,
                                         const double* h_J_regressor, const double* h_weights, const int32_t* h_parents, UhcSmplMesh** out) {
     // every check comes before the first HIP call
@@ -396,11 +333,11 @@ extern "C" int32_t uhc_smpl_mesh_create(int32_t n_vert, int32_t n_models, const 
     REFUSE("uhc_smpl_mesh_create", !h_parents, "h_parents is NULL");
     REFUSE("uhc_smpl_mesh_create", !sm_parents_ok(h_parents), "h_parents is no tree rooted at joint 0 with parent[j] < j (parent[0] = -1)");
     const size_t V = (size_t)n_vert, M = (size_t)n_models;
-    REFUSE("uhc_smpl_mesh_create", !all_finite(h_v_template, M * V * 3), "h_v_template holds a non-finite entry");
-    REFUSE("uhc_smpl_mesh_create", !all_finite(h_shapedirs, M * V * 3 * UHC_SM_NBETA), "h_shapedirs holds a non-finite entry");
-    REFUSE("uhc_smpl_mesh_create", !all_finite(h_posedirs, M * V * 3 * UHC_SM_NFEAT), "h_posedirs holds a non-finite entry");
-    REFUSE("uhc_smpl_mesh_create", !all_finite(h_J_regressor, M * UHC_SM_NJ * V), "h_J_regressor holds a non-finite entry");
-    REFUSE("uhc_smpl_mesh_create", !all_finite(h_weights, M * V * UHC_SM_NJ), "h_weights holds a non-finite entry");
+    REFUSE("uhc_smpl_mesh_create", !uhc_all_finite(h_v_template, M * V * 3), "h_v_template holds a non-finite entry");
+    REFUSE("uhc_smpl_mesh_create", !uhc_all_finite(h_shapedirs, M * V * 3 * UHC_SM_NBETA), "h_shapedirs holds a non-finite entry");
+    REFUSE("uhc_smpl_mesh_create", !uhc_all_finite(h_posedirs, M * V * 3 * UHC_SM_NFEAT), "h_posedirs holds a non-finite entry");
+    REFUSE("uhc_smpl_mesh_create", !uhc_all_finite(h_J_regressor, M * UHC_SM_NJ * V), "h_J_regressor holds a non-finite entry");
+    REFUSE("uhc_smpl_mesh_create", !uhc_all_finite(h_weights, M * V * UHC_SM_NJ), "h_weights holds a non-finite entry");
 
     // the tables as the kernel wants them: posedirs by vertex tile and coordinate, K padded; the skin weights as lists without their zeros (adding 0 x changes no sum)
     const int nt = sm_vert_tiles(n_vert);
@@ -427,12 +364,12 @@ extern "C" int32_t uhc_smpl_mesh_create(int32_t n_vert, int32_t n_models, const 
     *S = UhcSmplMesh{};
     S->n_vert = n_vert, S->n_vtiles = nt, S->n_models = n_models, S->nw = nw;
     for (int j = 0; j < UHC_SM_NJ; j++) S->parents[j] = h_parents[j];
-    hipError_t e = upload(&S->d_v_template, h_v_template, M * V * 3);
-    if (e == hipSuccess) e = upload(&S->d_shapedirs, h_shapedirs, M * V * 3 * UHC_SM_NBETA);
-    if (e == hipSuccess) e = upload(&S->d_jreg, h_J_regressor, M * UHC_SM_NJ * V);
-    if (e == hipSuccess) e = upload(&S->d_posedirs, (const double*)packed.data(), M * nb);
-    if (e == hipSuccess) e = upload(&S->d_wj, (const int*)wj.data(), M * vpad * nw);
-    if (e == hipSuccess) e = upload(&S->d_ww, (const double*)ww.data(), M * vpad * nw);
+    hipError_t e = uhc_upload(&S->d_v_template, h_v_template, M * V * 3);
+    if (e == hipSuccess) e = uhc_upload(&S->d_shapedirs, h_shapedirs, M * V * 3 * UHC_SM_NBETA);
+    if (e == hipSuccess) e = uhc_upload(&S->d_jreg, h_J_regressor, M * UHC_SM_NJ * V);
+    if (e == hipSuccess) e = uhc_upload(&S->d_posedirs, (const double*)packed.data(), M * nb);
+    if (e == hipSuccess) e = uhc_upload(&S->d_wj, (const int*)wj.data(), M * vpad * nw);
+    if (e == hipSuccess) e = uhc_upload(&S->d_ww, (const double*)ww.data(), M * vpad * nw);
     if (e != hipSuccess) {
         uhc_smpl_mesh_free(S);
         return uhc_internal_set_error((std::string("uhc_smpl_mesh_create: ") + hipGetErrorString(e)).c_str());
@@ -470,14 +407,14 @@ extern "C" int32_t uhc_smpl_mesh(void* stream, UhcSmplMesh* mesh, int32_t n_seq,
     REFUSE("uhc_smpl_mesh", !d_bad, "d_bad is NULL");
     const int tiles_per_seq = sm_row_tiles(row_cap);
     const long long blocks = ((long long)n_seq * tiles_per_seq + SM_WAVES - 1) / SM_WAVES;
-    REFUSE("uhc_smpl_mesh", blocks > 0x7fffffffLL || (long long)n_seq * UHC_SM_NJ > 0x7fffffffLL, "n_seq x row_cap is beyond one launch");
+    REFUSE("uhc_smpl_mesh", !uhc_launch_fits(blocks) || !uhc_launch_fits((long long)n_seq * UHC_SM_NJ), "n_seq x row_cap is beyond one launch");
     if (n_seq == 0) {
         if (h_bad) *h_bad = 0;
         return 0;
     }
     // (the check that reads the handle: behind the empty return, still before the first HIP call)
     const long long shape_blocks = (long long)n_seq * (((long long)UHC_SM_TILE * mesh->n_vtiles + 255) / 256);
-    REFUSE("uhc_smpl_mesh", shape_blocks > 0x7fffffffLL, "n_seq x n_vert is beyond one launch");
+    REFUSE("uhc_smpl_mesh", !uhc_launch_fits(shape_blocks), "n_seq x n_vert is beyond one launch");
     hipStream_t st = (hipStream_t)stream;
     const size_t vpad = (size_t)UHC_SM_TILE * mesh->n_vtiles;
     if ((size_t)n_seq > mesh->cap_seq) {  // (hipFree waits for the device: no kernel of an earlier call still reads the old buffers)
@@ -524,9 +461,5 @@ extern "C" int32_t uhc_smpl_mesh(void* stream, UhcSmplMesh* mesh, int32_t n_seq,
         hipLaunchKernelGGL(uhc_smpl_means_kernel, dim3((unsigned)((n_seq * UHC_SF_NMETRIC + 255) / 256)), dim3(256), 0, st, A);
         HIP_OK(hipGetLastError());
     }
-    if (h_bad) {  // the caller wants the count now: the one place that waits for the stream
-        HIP_OK(hipMemcpyAsync(h_bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-    }
-    return 0;
+    return uhc_return_bad(h_bad, d_bad, st);
 }

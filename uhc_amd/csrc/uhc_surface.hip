@@ -1,8 +1,8 @@
-// Contact quality of a motion on the device: uhc_surface_create / _free / _metrics, uhc_eval_record_pose (include/uhc_amd.h).
+// Contact quality of a motion on the device: uhc_surface_create / _free / _metrics (include/uhc_amd.h).
 //
 // Penetration, skate, float and contact count of a sequence of body poses (reference: compute_penetration / compute_skate, uhc/smpllib/smpl_eval.py:125-149,
 // there on SMPL surface vertices; here on the convex-hull vertices every compiled model carries in the body frame).  The poses are read where they lie:
-// a pose record (uhc_eval_record_pose appends xpos / xquat of bodies 1 .. 24 beside uhc_eval_record's rows) or the clip bank's frame records.
+// a pose record (uhc_eval.hip: uhc_eval_record_pose appends xpos / xquat of bodies 1 .. 24 beside uhc_eval_record's rows) or the clip bank's frame records.
 //
 //   uhc_surface_rows_kernel      one wave per (sequence, row), four waves per workgroup.  Lanes 0 .. n_body - 1 load the row's and the next row's body poses,
 //                                turn the quaternions into matrices and put both into the wave's slice of LDS (24 doubles a body); the vertices are dealt to
@@ -10,32 +10,22 @@
 //                                finishes with xor butterflies (32, 16, .., 1: every lane ends with the same bits, in an order fixed by the lane numbers alone).
 //                                The arithmetic of a vertex is uhc_surface_math.h, which the CPU test compiles for the host.
 //   uhc_surface_means_kernel     one thread per (sequence, metric): the mean over the sequence's rows in row order.
-//   uhc_eval_record_pose_kernel  one wave per env, four envs per workgroup: the 72 + 96 doubles of the row uhc_eval_record is about to append.  It reads the
-//                                row counter and leaves it to uhc_eval_record, which is enqueued behind it on the same stream.
 // No floating-point atomics; the one counter that is added to (d_bad) is an integer.  No index or counter, whatever it holds, sends a read or a write outside
-// the arrays: row counts are clamped to 0 .. row_cap, a sequence whose rows leave 0 .. n_rows_total is skipped, a model index outside the range reads as 0.
+// the arrays (uhc_seq.h: row counts are clamped to 0 .. row_cap, a sequence whose rows leave 0 .. n_rows_total is skipped, a model index outside the range
+// reads as 0).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/uhc_amd.h"
+#include "uhc_api_check.h"
 
-#include <cmath>
-#include <string>
 #include <vector>
 
 #pragma clang fp contract(off)
+#include "uhc_seq.h"
 #include "uhc_surface_math.h"
 
 #define SF_WAVES 4  // waves per workgroup
-#define SF_POSE_NBODY 24
-#define SF_POSE_ROW (7 * SF_POSE_NBODY)  // a pose record's row: [24][3] positions, then [24][4] quaternions
-
-extern "C" int uhc_internal_set_error(const char* msg);
-#define HIP_OK(expr)                                                                                                          \
-    do {                                                                                                                      \
-        hipError_t e__ = (expr);                                                                                              \
-        if (e__ != hipSuccess) return uhc_internal_set_error((std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); \
-    } while (0)
 
 struct UhcSurface {
     int n_body, n_vert, n_models;
@@ -57,36 +47,6 @@ struct SurfaceArgs {
     int* bad;
 };
 
-__device__ __forceinline__ int sf_rows_of(const SurfaceArgs& A, int s) {  // whatever the entry holds, the rows read lie inside the arrays
-    const int r = A.seq_rows[s];
-    return r < 0 ? 0 : (r > A.row_cap ? A.row_cap : r);
-}
-
-// the sequence's first global row, or -1 when its T rows would leave 0 .. n_rows_total (the sequence is then skipped)
-__device__ __forceinline__ long long sf_start_of(const SurfaceArgs& A, int s, int T) {
-    const long long g = A.seq_start[s];
-    return g >= 0 && g <= A.n_rows_total - T ? g : -1;
-}
-
-__device__ __forceinline__ double sf_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ int sf_wave_sum(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ double sf_wave_min(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double o = __shfl_xor(v, m);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 __device__ __forceinline__ UhcSfPose sf_lds_pose(const double* p) {
     UhcSfPose P;
 #pragma unroll
@@ -103,13 +63,12 @@ __global__ void __launch_bounds__(64 * SF_WAVES) uhc_surface_rows_kernel(const S
     // (no wave leaves before the barrier: one without a row loads nothing and stores nothing)
     const bool in_grid = R < (long long)A.n_seq * A.row_cap;
     const int s = in_grid ? (int)(R / A.row_cap) : 0, r = in_grid ? (int)(R % A.row_cap) : 0;
-    const int T = in_grid ? sf_rows_of(A, s) : 0;
-    const long long g0 = in_grid ? sf_start_of(A, s, T) : -1;
+    const int T = in_grid ? uhc_seq_rows(A.seq_rows[s], A.row_cap) : 0;
+    const long long g0 = in_grid ? uhc_seq_start(A.seq_start[s], T, A.n_rows_total) : -1;
     const bool valid = in_grid && r < T && g0 >= 0;
     const bool has_next = valid && r + 1 < T;
     const long long g = valid ? g0 + r : 0;  // (g + 1 < g0 + T <= n_rows_total where has_next)
-    int model = valid && A.seq_model ? A.seq_model[s] : 0;
-    model = model >= 0 && model < A.n_models ? model : 0;
+    const int model = uhc_seq_model(valid ? A.seq_model : nullptr, s, A.n_models);  // (a wave without a row reads no table)
 
     double* mine = sf_lds + (size_t)wave * A.n_body * 2 * UHC_SF_POSE_DOUBLES;
     bool ok0 = true, ok1 = true;
@@ -148,20 +107,12 @@ __global__ void __launch_bounds__(64 * SF_WAVES) uhc_surface_rows_kernel(const S
     }
     // (every lane of every wave takes part in the butterflies)
     UhcSfAcc w;
-    w.pen_sum = sf_wave_sum(a.pen_sum), w.skate_sum = sf_wave_sum(a.skate_sum), w.h_min = sf_wave_min(a.h_min);
-    w.pen_n = sf_wave_sum(a.pen_n), w.skate_n = sf_wave_sum(a.skate_n), w.contact_n = sf_wave_sum(a.contact_n), w.above_n = sf_wave_sum(a.above_n);
+    w.pen_sum = uhc_xor_sum<32>(a.pen_sum), w.skate_sum = uhc_xor_sum<32>(a.skate_sum), w.h_min = uhc_xor_min<32>(a.h_min);
+    w.pen_n = uhc_xor_sum<32>(a.pen_n), w.skate_n = uhc_xor_sum<32>(a.skate_n), w.contact_n = uhc_xor_sum<32>(a.contact_n), w.above_n = uhc_xor_sum<32>(a.above_n);
 
     if (valid && lane == 0) {
-        const double nan = __longlong_as_double(0x7ff8000000000000LL);
-        double* out = A.row_out + (size_t)g * UHC_SF_NMETRIC;
-        if (row_ok) {
-            uhc_sf_finish(w, A.n_vert, has_next, out);
-            if (has_next && !next_ok) out[UHC_SF_SKATE] = nan;
-        } else {
-            out[UHC_SF_PEN] = out[UHC_SF_FLOAT] = out[UHC_SF_CONTACT] = nan;
-            if (has_next) out[UHC_SF_SKATE] = nan;
-            atomicAdd(A.bad, 1);  // one count per bad row: by the wave that owns it
-        }
+        uhc_sf_store_row(A.row_out + (size_t)g * UHC_SF_NMETRIC, w, A.n_vert, has_next, row_ok, next_ok);
+        if (!row_ok) atomicAdd(A.bad, 1);  // one count per bad row: by the wave that owns it
     }
 }
 
@@ -169,45 +120,16 @@ __global__ void __launch_bounds__(256) uhc_surface_means_kernel(const SurfaceArg
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= A.n_seq * UHC_SF_NMETRIC) return;
     const int s = idx / UHC_SF_NMETRIC, k = idx % UHC_SF_NMETRIC;
-    const int T = sf_rows_of(A, s);
-    const long long g0 = sf_start_of(A, s, T);
+    const int T = uhc_seq_rows(A.seq_rows[s], A.row_cap);
+    const long long g0 = uhc_seq_start(A.seq_start[s], T, A.n_rows_total);
     if (g0 < 0) {  // the sequence is skipped: nothing of it is read or written
         if (k == 0) atomicAdd(A.bad, 1);
         return;
     }
-    int n = T - (k == UHC_SF_SKATE ? 1 : 0);
-    n = n < 0 ? 0 : n;
-    double sum = 0.0;
-    for (int r = 0; r < n; r++) sum += A.row_out[(size_t)(g0 + r) * UHC_SF_NMETRIC + k];
-    A.seq_means[idx] = n > 0 ? sum / n : __longlong_as_double(0x7ff8000000000000LL);  // np.mean of an empty array
-}
-
-// ------------------------------------------------------------------ the pose record
-struct PoseArgs {
-    int phase, n_env, nbody, row_cap;
-    const double *xpos, *xquat;  // [n_env][nbody][3], [n_env][nbody][4] (body 0 = the world)
-    const int *done, *alive, *rows;
-    double* pose;  // [n_env][row_cap][168]
-};
-
-__global__ void __launch_bounds__(64 * SF_WAVES) uhc_eval_record_pose_kernel(const PoseArgs A) {
-    const int lane = threadIdx.x & 63, e = blockIdx.x * SF_WAVES + (threadIdx.x >> 6);
-    if (e >= A.n_env) return;
-    if (A.alive[e] == 0) return;
-    if (!(A.phase == 0 || A.done[e] != 0)) return;  // uhc_eval_record's rule for a snapshot
-    const int rows = A.rows[e];
-    if (rows < 0 || rows >= A.row_cap) return;  // (uhc_eval_record counts the overflow)
-    double* out = A.pose + ((size_t)e * A.row_cap + rows) * SF_POSE_ROW;
-    const double* x = A.xpos + (size_t)e * A.nbody * 3 + 3;   // bodies 1 .. 24
-    const double* q = A.xquat + (size_t)e * A.nbody * 4 + 4;
-    for (int j = lane; j < 3 * SF_POSE_NBODY; j += 64) out[j] = x[j];
-    for (int j = lane; j < 4 * SF_POSE_NBODY; j += 64) out[3 * SF_POSE_NBODY + j] = q[j];
+    A.seq_means[idx] = uhc_seq_mean(A.row_out, UHC_SF_NMETRIC, k, g0, T - (k == UHC_SF_SKATE ? 1 : 0));  // (the skate: over the T - 1 pairs of rows)
 }
 
 // ------------------------------------------------------------------ C-ABI (include/uhc_amd.h)
-#define REFUSE(fn, cond, what) \
-    if (cond) return uhc_internal_set_error(fn ": " what)
-
 extern "C" int32_t uhc_surface_create(int32_t n_body, int32_t n_vert, int32_t n_models, const int32_t* h_vert_body, const double* h_vert_radius,
                                       const double* h_vert, UhcSurface** out) {
     // every check comes before the first HIP call
@@ -224,18 +146,15 @@ extern "C" int32_t uhc_surface_create(int32_t n_body, int32_t n_vert, int32_t n_
         REFUSE("uhc_surface_create", h_vert_radius && !(std::isfinite(h_vert_radius[v]) && h_vert_radius[v] >= 0.0), "h_vert_radius holds a negative or non-finite radius");
     }
     const size_t n3 = (size_t)n_models * n_vert * 3;
-    for (size_t i = 0; i < n3; i++) REFUSE("uhc_surface_create", !std::isfinite(h_vert[i]), "h_vert holds a non-finite coordinate");
+    REFUSE("uhc_surface_create", !uhc_all_finite(h_vert, n3), "h_vert holds a non-finite coordinate");
     std::vector<double> radius(n_vert, 0.0);
     if (h_vert_radius) radius.assign(h_vert_radius, h_vert_radius + n_vert);
     UhcSurface* S = new UhcSurface();
+    *S = UhcSurface{};
     S->n_body = n_body, S->n_vert = n_vert, S->n_models = n_models;
-    S->d_vert_body = nullptr, S->d_vert_radius = nullptr, S->d_vert = nullptr;
-    hipError_t e = hipMalloc((void**)&S->d_vert_body, sizeof(int) * n_vert);
-    if (e == hipSuccess) e = hipMalloc((void**)&S->d_vert_radius, sizeof(double) * n_vert);
-    if (e == hipSuccess) e = hipMalloc((void**)&S->d_vert, sizeof(double) * n3);
-    if (e == hipSuccess) e = hipMemcpy(S->d_vert_body, h_vert_body, sizeof(int) * n_vert, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(S->d_vert_radius, radius.data(), sizeof(double) * n_vert, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(S->d_vert, h_vert, sizeof(double) * n3, hipMemcpyHostToDevice);
+    hipError_t e = uhc_upload(&S->d_vert_body, h_vert_body, n_vert);
+    if (e == hipSuccess) e = uhc_upload(&S->d_vert_radius, radius.data(), n_vert);
+    if (e == hipSuccess) e = uhc_upload(&S->d_vert, h_vert, n3);
     if (e != hipSuccess) {
         uhc_surface_free(S);
         return uhc_internal_set_error((std::string("uhc_surface_create: ") + hipGetErrorString(e)).c_str());
@@ -246,9 +165,9 @@ extern "C" int32_t uhc_surface_create(int32_t n_body, int32_t n_vert, int32_t n_
 
 extern "C" void uhc_surface_free(UhcSurface* S) {
     if (!S) return;
-    if (S->d_vert_body) (void)hipFree(S->d_vert_body);
-    if (S->d_vert_radius) (void)hipFree(S->d_vert_radius);
-    if (S->d_vert) (void)hipFree(S->d_vert);
+    void* all[] = {S->d_vert_body, S->d_vert_radius, S->d_vert};
+    for (void* p : all)
+        if (p) (void)hipFree(p);
     delete S;
 }
 
@@ -271,7 +190,7 @@ extern "C" int32_t uhc_surface_metrics(void* stream, const UhcSurface* surf, int
     REFUSE("uhc_surface_metrics", !d_seq_means, "d_seq_means is NULL");
     REFUSE("uhc_surface_metrics", !d_bad, "d_bad is NULL");
     const long long blocks = ((long long)n_seq * row_cap + SF_WAVES - 1) / SF_WAVES;
-    REFUSE("uhc_surface_metrics", blocks > 0x7fffffffLL || (long long)n_seq * UHC_SF_NMETRIC > 0x7fffffffLL, "n_seq x row_cap is beyond one launch");
+    REFUSE("uhc_surface_metrics", !uhc_launch_fits(blocks) || !uhc_launch_fits((long long)n_seq * UHC_SF_NMETRIC), "n_seq x row_cap is beyond one launch");
     if (n_seq == 0) {
         if (h_bad) *h_bad = 0;
         return 0;
@@ -292,30 +211,5 @@ extern "C" int32_t uhc_surface_metrics(void* stream, const UhcSurface* surf, int
     HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(uhc_surface_means_kernel, dim3((unsigned)((n_seq * UHC_SF_NMETRIC + 255) / 256)), dim3(256), 0, s, A);
     HIP_OK(hipGetLastError());
-    if (h_bad) {  // the caller wants the count now: the one place that waits for the stream
-        HIP_OK(hipMemcpyAsync(h_bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-    }
-    return 0;
-}
-
-extern "C" int32_t uhc_eval_record_pose(void* stream, int32_t phase, int32_t n_env, int32_t nbody, int32_t row_cap, const double* d_xpos, const double* d_xquat,
-                                        const int32_t* d_done, const int32_t* d_alive, const int32_t* d_rows, double* d_pose) {
-    REFUSE("uhc_eval_record_pose", phase != 0 && phase != 1, "phase must be 0 (before the step) or 1 (after it)");
-    REFUSE("uhc_eval_record_pose", n_env < 0, "n_env < 0");
-    REFUSE("uhc_eval_record_pose", nbody < SF_POSE_NBODY + 1, "nbody must be at least 25 (the world body comes first, a row holds 24 poses)");
-    REFUSE("uhc_eval_record_pose", row_cap <= 0, "row_cap <= 0");
-    REFUSE("uhc_eval_record_pose", !d_xpos, "d_xpos is NULL");
-    REFUSE("uhc_eval_record_pose", !d_xquat, "d_xquat is NULL");
-    REFUSE("uhc_eval_record_pose", phase == 1 && !d_done, "d_done is NULL");
-    REFUSE("uhc_eval_record_pose", !d_alive, "d_alive is NULL");
-    REFUSE("uhc_eval_record_pose", !d_rows, "d_rows is NULL");
-    REFUSE("uhc_eval_record_pose", !d_pose, "d_pose is NULL");
-    if (n_env == 0) return 0;
-    PoseArgs A = {};
-    A.phase = phase, A.n_env = n_env, A.nbody = nbody, A.row_cap = row_cap, A.xpos = d_xpos, A.xquat = d_xquat, A.done = d_done, A.alive = d_alive, A.rows = d_rows;
-    A.pose = d_pose;
-    hipLaunchKernelGGL(uhc_eval_record_pose_kernel, dim3((unsigned)((n_env + SF_WAVES - 1) / SF_WAVES)), dim3(64 * SF_WAVES), 0, (hipStream_t)stream, A);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return uhc_return_bad(h_bad, d_bad, s);
 }

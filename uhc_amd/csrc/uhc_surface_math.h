@@ -4,7 +4,7 @@
 // Straight-line float64 on fixed-size values: no run-time array index, no allocation, nothing of the HIP runtime.
 //
 // What is shared are the PIECES of one vertex; the sums over the vertices belong to the caller (per-lane partial sums and a wave reduction on the device, a
-// loop on the host -- uhc_sf_row_serial below, the restatement the CPU test runs):
+// loop on the host -- uhc_sf_row_serial below, which the CPU test runs); how the finished row is stored is shared again, uhc_sf_store_row:
 //   uhc_sf_pose        a body's pose as the kernel keeps it: position and the rotation matrix of its quaternion
 //   uhc_sf_world       w = xpos + R(xquat) v
 //   uhc_sf_height      h = w.z - radius - floor_z
@@ -12,6 +12,8 @@
 //   uhc_sf_slide       |w_xy[r + 1] - w_xy[r]|
 #pragma once
 #include <math.h>
+
+#include "uhc_seq.h"  // uhc_nan
 
 #if defined(__HIPCC__)
 #define UHC_SF_HD __host__ __device__ __forceinline__
@@ -107,6 +109,18 @@ UHC_SF_HD void uhc_sf_finish(const UhcSfAcc& a, int n_vert, bool has_next, doubl
     out[UHC_SF_CONTACT] = (double)a.contact_n;
 }
 
+// The row as every path stores it -- the kernels (uhc_surface.hip, uhc_smpl_mesh.hip) and the host loop below: uhc_sf_finish's values where the row's own poses
+// are finite (row_ok), with the skate NaN where the next row's are not (next_ok); NaN throughout for a bad row.  The skate slot is left alone without a next row.
+UHC_SF_HD void uhc_sf_store_row(double* out, const UhcSfAcc& acc, int n_vert, bool has_next, bool row_ok, bool next_ok) {
+    if (row_ok) {
+        uhc_sf_finish(acc, n_vert, has_next, out);
+        if (has_next && !next_ok) out[UHC_SF_SKATE] = uhc_nan();
+    } else {
+        out[UHC_SF_PEN] = out[UHC_SF_FLOAT] = out[UHC_SF_CONTACT] = uhc_nan();
+        if (has_next) out[UHC_SF_SKATE] = uhc_nan();
+    }
+}
+
 // One row, the sums over the vertices as a plain loop in vertex order.  pos0 / quat0: [n_body][3] / [n_body][4] of row r; pos1 / quat1: of row r + 1 (read only
 // when has_next); vert [n_vert][3] in the body frame, vert_body [n_vert] (0 .. n_body - 1), vert_radius [n_vert] or NULL.  A non-finite pose number in row r:
 // the four values are NaN; in row r + 1: the skate is.  Returns 1 when row r is such a row (the caller's `bad` count), else 0.
@@ -124,13 +138,6 @@ inline int uhc_sf_row_serial(int n_body, int n_vert, const int* vert_body, const
         const UhcSfPose P1 = has_next ? uhc_sf_pose(pos1 + 3 * b, quat1 + 4 * b) : P0;
         uhc_sf_acc_vertex(a, P0, P1, has_next, vert[3 * v], vert[3 * v + 1], vert[3 * v + 2], vert_radius ? vert_radius[v] : 0.0, floor_z);
     }
-    uhc_sf_finish(a, n_vert, has_next, out);
-    const double nan = NAN;
-    if (!ok0) {
-        out[UHC_SF_PEN] = out[UHC_SF_FLOAT] = out[UHC_SF_CONTACT] = nan;
-        if (has_next) out[UHC_SF_SKATE] = nan;
-    } else if (has_next && !ok1) {
-        out[UHC_SF_SKATE] = nan;
-    }
+    uhc_sf_store_row(out, a, n_vert, has_next, ok0, ok1);
     return ok0 ? 0 : 1;
 }
