@@ -198,6 +198,10 @@ class AgentCopycat(AgentPPO):
         rs = cp["running_state"]  # copied INTO the agent's filter: its device tensors are referenced by the captured rollout graphs
         if rs is not None and self.running_state is not None:  # (the reference accepts checkpoints without a filter: the current one stays)
             self.running_state.set_mean_std(np.asarray(rs.rs.mean), np.asarray(rs.rs._S), int(rs.rs.n))
+            if (self.running_state.demean, self.running_state.destd, self.running_state.clip) != (rs.demean, rs.destd, rs.clip):
+                # uhc_filter_apply takes the three BY VALUE: a captured rollout graph would go on normalising with the old ones -- capture again
+                for R in getattr(self, "_ro_cache", {}).values():
+                    R.graphs = None
             self.running_state.demean, self.running_state.destd, self.running_state.clip = rs.demean, rs.destd, rs.clip
         to_device(self.device, self.policy_net, self.value_net)
         # every rank has just loaded the same statistics: they are the shared base of the next merge, not new samples of this rank

@@ -37,7 +37,12 @@ __global__ void __launch_bounds__(256) uhc_rollout_act_kernel(int n_env, int T, 
     const int k = j - obs_dim;
     const double m = mean[(size_t)env * act_dim + k];
     double a = m;
-    if (mean_flags[(size_t)t * n_env + env] == 0.0) a = __dadd_rn(m, __dmul_rn(exp(log_std[k]), noise[(size_t)env * act_dim + k]));
+    if (mean_flags[(size_t)t * n_env + env] == 0.0) {
+        // (__dmul_rn / __dadd_rn are a plain * and + to this compiler, which then fuses them under its default -ffp-contract: the pragma is what keeps the two roundings)
+#pragma clang fp contract(off)
+        const double p = exp(log_std[k]) * noise[(size_t)env * act_dim + k];
+        a = m + p;
+    }
     actions[((size_t)env * T + t) * act_dim + k] = a;
     action[(size_t)env * act_dim + k] = a;
 }
@@ -179,7 +184,7 @@ __global__ void __launch_bounds__(256) uhc_filter_apply_kernel(const double* __r
         const double var = n > 1.0 ? S_run[col] / (n - 1.0) : M * M;
         y = y / (sqrt(var) + 1e-8);
     }
-    if (clip != 0.0) y = fmin(fmax(y, -clip), clip);
+    if (clip != 0.0) y = y < -clip ? -clip : (y > clip ? clip : y);  // (comparisons, not fmin / fmax: those return the bound for a NaN; np.clip / torch.clamp keep it)
     out[idx] = y;
 }
 
