@@ -12,10 +12,11 @@ import itertools
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+from tests import probe_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
@@ -66,18 +67,8 @@ def model_class(name):
 def build_probe():
     """uhc_plan.cpp + tests/plan_probe.cpp -> uhc_amd/csrc/build/plan_probe.so with the host compiler: no hipcc, no HIP runtime (the HIP headers only for the struct
     definitions of uhc_device.h)."""
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "plan_probe.so")
-    srcs = [os.path.join(ROOT, "tests", "plan_probe.cpp"), os.path.join(CSRC, "uhc_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("uhc_plan.h", "uhc_host.h", "uhc_device.h", "uhc_step_words.h")] + [os.path.join(ROOT, "include", "uhc_amd.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        tmp = so + f".{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-fPIC", "-shared", "-fvisibility=hidden", "-D__HIP_PLATFORM_AMD__",
-                               "-I" + os.path.join(rocm, "include"), "-I" + CSRC] + srcs + ["-o", tmp])
-        os.replace(tmp, so)
-    return so
+    return probe_build.build_probe("plan_probe.so", ["tests/plan_probe.cpp", "uhc_amd/csrc/uhc_plan.cpp"],
+                                   ["uhc_amd/csrc/" + h for h in ("uhc_plan.h", "uhc_host.h", "uhc_device.h", "uhc_step_words.h")] + ["include/uhc_amd.h"], probe_build.HIP_STRUCT_FLAGS)
 
 
 class Probe:

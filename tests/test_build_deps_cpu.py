@@ -66,6 +66,22 @@ def test_post_processing_units_and_step_units_stay_apart(deps):
         assert names[u] & set(POST_HEADERS) == set(), (u, names[u])
 
 
+def test_the_internal_seams_header_is_read_by_the_units_on_either_side_of_a_seam_and_no_other(deps):
+    # uhc_internal.h declares the launchers and accessors the units share: the units that DEFINE one (the three kernel units, uhc_capi.cpp) and the two that CALL
+    # them read it, so a prototype cannot differ between them; no step-kernel unit does (an edit of it rebuilds none of their objects, ~4 minutes), and nothing
+    # the step kernels include pulls it in
+    names, _ = deps
+    seams = {"uhc_batch_kernels.hip", "uhc_env.hip", "uhc_live.hip", "uhc_capi.cpp", "uhc_env_capi.cpp"}
+    assert {u for u in g.HIP_SOURCES if "uhc_internal.h" in names[u]} == seams
+    assert not any(u.startswith("uhc_k_") for u in seams)
+    for h in ("uhc_launch.h", "uhc_physics_impl.h", "uhc_device.h", "uhc_api_check.h", "uhc_device_env.h"):
+        assert '#include "uhc_internal.h"' not in open(os.path.join(CSRC, h)).read(), h
+    # the env's plan (and the struct of the batch's dims beside it): the unit that fills the struct and the unit that plans from it
+    assert {u for u in g.HIP_SOURCES if "uhc_env_plan.h" in names[u]} == {"uhc_capi.cpp", "uhc_env_capi.cpp"}
+    # uhc_internal_set_error's one declaration: its definer reads it too
+    assert "uhc_api_check.h" in names["uhc_capi.cpp"]
+
+
 def test_every_dependency_lies_inside_the_repository(deps):
     _, full = deps
     for u, d in full.items():
@@ -101,7 +117,7 @@ def test_an_edit_changes_the_keys_of_exactly_the_units_that_include_the_file(tmp
         assert all(f.startswith(str(tmp_path.resolve()) + os.sep) for f in g.unit_deps(s, flags, str(csrc)))
     before = keys()
     assert before == keys(CSRC)  # (same contents, same flags: same keys)
-    for edited in ("uhc_mpr.h", "uhc_primal.h", "uhc_device_env.h", "uhc_env.hip"):
+    for edited in ("uhc_mpr.h", "uhc_primal.h", "uhc_device_env.h", "uhc_env.hip", "uhc_internal.h"):
         with open(csrc / edited, "a") as f:
             f.write("// an edit\n")
         after = keys()

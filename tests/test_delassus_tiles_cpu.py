@@ -3,28 +3,18 @@ host compiler, emulates the 16 x 16 x 4 matrix instruction from the lane maps an
 dofs, random trees of 1 / 6 / 75 / 99 / 128 dofs, the shipped humanoid's tree and its ball-joint variant's, at every row count on both sides of a tile edge, with
 dense rows in lane 0 and in the last lane -- against the naive double loop over the common chain prefix; and the chain-position masks against the chains
 themselves for every (dof, ancestor) pair."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
+from tests import probe_build
+
 NEFC = (1, 15, 16, 17, 31, 32, 33, 48, 49, 63, 64)
 BUILTIN_TREES = 6
 
 
 def build_probe(tag, extra=()):
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "delassus_tiles_probe" + tag)
-    src = os.path.join(ROOT, "tests", "delassus_tiles_probe.cpp")
-    deps = [src, os.path.join(CSRC, "uhc_delassus_tiles.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        tmp = exe + f".{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + CSRC, *extra, src, "-o", tmp])
-        os.replace(tmp, exe)
-    return exe
+    return probe_build.build_probe("delassus_tiles_probe" + tag, ["tests/delassus_tiles_probe.cpp"], ["uhc_amd/csrc/uhc_delassus_tiles.h"], ("-Wall", "-Werror", *extra))
 
 
 @pytest.fixture(scope="module")
@@ -70,16 +60,9 @@ def test_the_planners_chain_masks_are_the_planners_chains(name):
     import numpy as np
 
     from tests.test_batch_plan_cpu import Probe, model_class
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "chainmask_probe.so")
-    srcs = [os.path.join(ROOT, "tests", "chainmask_probe.cpp"), os.path.join(CSRC, "uhc_plan.cpp")]
-    deps = srcs + [os.path.join(ROOT, "tests", "plan_probe.cpp")] + [os.path.join(CSRC, h) for h in ("uhc_plan.h", "uhc_host.h", "uhc_device.h", "uhc_step_words.h", "uhc_delassus_tiles.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + f".{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-fPIC", "-shared", "-fvisibility=hidden", "-D__HIP_PLATFORM_AMD__",
-                               "-I" + os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include"), "-I" + CSRC] + srcs + ["-o", tmp])
-        os.replace(tmp, so)
+    so = probe_build.build_probe("chainmask_probe.so", ["tests/chainmask_probe.cpp", "uhc_amd/csrc/uhc_plan.cpp"],
+                                 ["tests/plan_probe.cpp"] + ["uhc_amd/csrc/" + h for h in ("uhc_plan.h", "uhc_host.h", "uhc_device.h", "uhc_step_words.h", "uhc_delassus_tiles.h")],
+                                 probe_build.HIP_STRUCT_FLAGS)
     p = Probe(so)
     m, ctrl = model_class(name)
     words, _ = p.plan(m, ctrl, 64)

@@ -5,13 +5,13 @@ makes BEFORE its first HIP call; the config key."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import probe_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
 NAMES = ["root_dist", "vel_dist", "accel_dist", "mpjpe_g", "pa_mpjpe", "mpjpe"]  # a row of the kernels' output, in order
 SENTINEL = -7.0
 FAKE = C.c_void_p(0x1000)  # a non-null "device pointer": every call here is refused or has n_env == 0 -- nothing is launched and nothing dereferences it
@@ -19,17 +19,7 @@ FAKE = C.c_void_p(0x1000)  # a non-null "device pointer": every call here is ref
 
 def build_probe():
     """tests/eval_metrics_probe.cpp + uhc_eval_metrics.h -> uhc_amd/csrc/build/eval_metrics_probe.so with the host compiler: no hipcc, no HIP header."""
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "eval_metrics_probe.so")
-    src = os.path.join(ROOT, "tests", "eval_metrics_probe.cpp")
-    deps = [src, os.path.join(CSRC, "uhc_eval_metrics.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + f".{os.getpid()}.tmp"
-        # (-ffp-contract=off: products and sums rounded separately, as the device unit is compiled)
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=hidden", "-I" + CSRC, src, "-o", tmp])
-        os.replace(tmp, so)
-    return so
+    return probe_build.build_probe("eval_metrics_probe.so", ["tests/eval_metrics_probe.cpp"], ["uhc_amd/csrc/uhc_eval_metrics.h"], probe_build.NO_CONTRACT)
 
 
 @pytest.fixture(scope="module")

@@ -6,12 +6,11 @@ workgroups, all of which the general tier's consumers wait for: the chunks must 
 n_chunks x n_env; a chunk size of 0 or of the whole step must give the whole-step launch's sizes."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
+from tests import probe_build
+
 N_SUBSTEPS = 15
 CHUNKS = (0, 1, 3, 5, 7, 8, 15, 16)
 N_ENVS = (1, 64, 1024, 4096)
@@ -19,18 +18,8 @@ KIB = 1024
 
 
 def build_probe():
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "fast_chunks_probe.so")
-    srcs = [os.path.join(ROOT, "tests", "fast_chunks_probe.cpp"), os.path.join(CSRC, "uhc_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("uhc_plan.h", "uhc_host.h", "uhc_device.h", "uhc_step_words.h")] + [os.path.join(ROOT, "include", "uhc_amd.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        tmp = so + f".{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-fPIC", "-shared", "-fvisibility=hidden", "-D__HIP_PLATFORM_AMD__",
-                               "-I" + os.path.join(rocm, "include"), "-I" + CSRC] + srcs + ["-o", tmp])
-        os.replace(tmp, so)
-    return so
+    return probe_build.build_probe("fast_chunks_probe.so", ["tests/fast_chunks_probe.cpp", "uhc_amd/csrc/uhc_plan.cpp"],
+                                   ["uhc_amd/csrc/" + h for h in ("uhc_plan.h", "uhc_host.h", "uhc_device.h", "uhc_step_words.h")] + ["include/uhc_amd.h"], probe_build.HIP_STRUCT_FLAGS)
 
 
 @pytest.fixture(scope="module")

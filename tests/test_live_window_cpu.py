@@ -4,30 +4,18 @@ resolves to the same global frame after the slide as before it, and a slice that
 (tests/live_window_cases.py), the model's rule being the header's: no read ever maps to a discarded frame."""
 import ctypes as C
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import probe_build
 from tests import live_window_cases as LW
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
 
 
 def build_probe():
     """tests/live_window_probe.cpp + uhc_live_window.h -> uhc_amd/csrc/build/live_window_probe.so with the host compiler: no hipcc, no HIP header."""
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "live_window_probe.so")
-    src = os.path.join(ROOT, "tests", "live_window_probe.cpp")
-    deps = [src, os.path.join(CSRC, "uhc_live_window.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + f".{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-fPIC", "-shared", "-fvisibility=hidden", "-I" + CSRC, src, "-o", tmp])
-        os.replace(tmp, so)
-    return so
+    return probe_build.build_probe("live_window_probe.so", ["tests/live_window_probe.cpp"], ["uhc_amd/csrc/uhc_live_window.h"])
 
 
 @pytest.fixture(scope="module")

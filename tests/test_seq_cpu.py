@@ -2,32 +2,20 @@
 the ordered mean) -- compiled for the host (tests/seq_probe.cpp) and run at the edges at which each can go wrong.  What the header promises is that no index,
 whatever it holds, leaves the arrays: every result here is checked to lie in its range, not only to be the expected one."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
+from tests import probe_build
+
 INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
 QNAN_BITS = 0x7ff8000000000000
 
 
 def build_probe():
     """tests/seq_probe.cpp + uhc_seq.h -> uhc_amd/csrc/build/seq_probe.so with the host compiler: no hipcc, no HIP header."""
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "seq_probe.so")
-    src = os.path.join(ROOT, "tests", "seq_probe.cpp")
-    deps = [src, os.path.join(CSRC, "uhc_seq.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + f".{os.getpid()}.tmp"
-        # (-ffp-contract=off: products and sums rounded separately, as the device units are compiled)
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=hidden", "-I" + CSRC, src, "-o", tmp])
-        os.replace(tmp, so)
-    return so
+    return probe_build.build_probe("seq_probe.so", ["tests/seq_probe.cpp"], ["uhc_amd/csrc/uhc_seq.h"], probe_build.NO_CONTRACT)
 
 
 @pytest.fixture(scope="module")

@@ -12,10 +12,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import probe_build
 from tests import smpl_convert_cases as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
 G = os.path.join(ROOT, "tests", "golden")
 SENTINEL = -7.0
 FAKE = C.c_void_p(0x1000)  # a non-null, 16-byte aligned "device pointer": every call here is refused or has n_frames == 0 -- nothing is launched, nothing dereferences it
@@ -23,17 +23,7 @@ FAKE = C.c_void_p(0x1000)  # a non-null, 16-byte aligned "device pointer": every
 
 def build_probe():
     """tests/smpl_convert_probe.cpp + uhc_smpl_convert.h -> uhc_amd/csrc/build/smpl_convert_probe.so with the host compiler: no hipcc, no HIP header."""
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "smpl_convert_probe.so")
-    src = os.path.join(ROOT, "tests", "smpl_convert_probe.cpp")
-    deps = [src, os.path.join(CSRC, "uhc_smpl_convert.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + f".{os.getpid()}.tmp"
-        # (-ffp-contract=off: products and sums rounded separately, as the device unit is compiled)
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=hidden", "-I" + CSRC, src, "-o", tmp])
-        os.replace(tmp, so)
-    return so
+    return probe_build.build_probe("smpl_convert_probe.so", ["tests/smpl_convert_probe.cpp"], ["uhc_amd/csrc/uhc_smpl_convert.h"], probe_build.NO_CONTRACT)
 
 
 @pytest.fixture(scope="module")

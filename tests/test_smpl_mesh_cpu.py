@@ -6,31 +6,22 @@ import ctypes as C
 import os
 import pickle
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import probe_build
 from tests import smpl_mesh_cases as MC
 from uhc_amd.smpllib import smpl_mesh as SM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
 FAKE = C.c_void_p(0x1000)  # a non-null "device pointer": every call here is refused or has nothing to do
 
 
 def build_probe():
     """tests/smpl_mesh_probe.cpp + the two math headers -> uhc_amd/csrc/build/smpl_mesh_probe.so with the host compiler: no hipcc, no HIP header."""
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "smpl_mesh_probe.so")
-    src = os.path.join(ROOT, "tests", "smpl_mesh_probe.cpp")
-    deps = [src, os.path.join(CSRC, "uhc_smpl_mesh_math.h"), os.path.join(CSRC, "uhc_surface_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + f".{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=hidden", "-I" + CSRC, src, "-o", tmp])
-        os.replace(tmp, so)
-    return so
+    return probe_build.build_probe("smpl_mesh_probe.so", ["tests/smpl_mesh_probe.cpp"], ["uhc_amd/csrc/uhc_smpl_mesh_math.h", "uhc_amd/csrc/uhc_surface_math.h"],
+                                   probe_build.NO_CONTRACT)
 
 
 @pytest.fixture(scope="module")

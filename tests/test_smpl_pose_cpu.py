@@ -12,11 +12,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import probe_build
 from tests import smpl_convert_cases as K
 from tests import smpl_pose_cases as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
 G = os.path.join(ROOT, "tests", "golden")
 FAKE = C.c_void_p(0x1000)  # a non-null, 16-byte aligned "device pointer": every call here is refused or has no rows -- nothing is launched, nothing dereferences it
 ODD = C.c_void_p(0x1008)   # 8-byte aligned only
@@ -24,17 +24,7 @@ ODD = C.c_void_p(0x1008)   # 8-byte aligned only
 
 def build_probe(name="smpl_pose_probe"):
     """tests/<name>.cpp + uhc_smpl_convert.h -> uhc_amd/csrc/build/<name>.so with the host compiler: no hipcc, no HIP header."""
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, name + ".so")
-    src = os.path.join(ROOT, "tests", name + ".cpp")
-    deps = [src, os.path.join(CSRC, "uhc_smpl_convert.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + f".{os.getpid()}.tmp"
-        # (-ffp-contract=off: products and sums rounded separately, as the device unit is compiled)
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=hidden", "-I" + CSRC, src, "-o", tmp])
-        os.replace(tmp, so)
-    return so
+    return probe_build.build_probe(name + ".so", ["tests/" + name + ".cpp"], ["uhc_amd/csrc/uhc_smpl_convert.h"], probe_build.NO_CONTRACT)
 
 
 @pytest.fixture(scope="module")

@@ -11,27 +11,18 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import probe_build
 from tests import surface_cases as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "uhc_amd", "csrc")
 FAKE = C.c_void_p(0x1000)  # a non-null "device pointer": every call here is refused or has nothing to do -- nothing is launched and nothing dereferences it
 ATOL = 1e-9  # mm
 
 
 def build_probe():
     """tests/surface_metrics_probe.cpp + uhc_surface_math.h -> uhc_amd/csrc/build/surface_metrics_probe.so with the host compiler: no hipcc, no HIP header."""
-    out_dir = os.path.join(CSRC, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "surface_metrics_probe.so")
-    src = os.path.join(ROOT, "tests", "surface_metrics_probe.cpp")
-    deps = [src, os.path.join(CSRC, "uhc_surface_math.h"), os.path.join(CSRC, "uhc_seq.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + f".{os.getpid()}.tmp"
-        # (-ffp-contract=off: products and sums rounded separately, as the device unit is compiled)
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=hidden", "-I" + CSRC, src, "-o", tmp])
-        os.replace(tmp, so)
-    return so
+    return probe_build.build_probe("surface_metrics_probe.so", ["tests/surface_metrics_probe.cpp"], ["uhc_amd/csrc/uhc_surface_math.h", "uhc_amd/csrc/uhc_seq.h"],
+                                   probe_build.NO_CONTRACT)
 
 
 @pytest.fixture(scope="module")

@@ -1,6 +1,6 @@
 // uhc_api_check.h -- the host side every C entry of the post-processing units and of the env layer shares: how a call is refused (by name, before the first HIP
 // call), how a failed HIP call is reported, and the few steps around a launch that each entry used to spell out for itself.  uhc_capi.cpp owns the error
-// string (uhc_last_error) and keeps its own macro over it.
+// string (uhc_last_error) and reports its own failed HIP calls through the same macro.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,7 +8,8 @@
 #include <cmath>
 #include <string>
 
-extern "C" int uhc_internal_set_error(const char* msg);  // uhc_capi.cpp: keeps the text for uhc_last_error, returns 1
+// uhc_capi.cpp (which includes this header too): keeps the text for uhc_last_error, returns 1.  Declared here, not in uhc_internal.h: uhc_rollout.hip reads this header alone
+extern "C" int uhc_internal_set_error(const char* msg);
 
 #define HIP_OK(expr)                                                                                                          \
     do {                                                                                                                      \

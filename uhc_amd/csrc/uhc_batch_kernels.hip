@@ -1,5 +1,6 @@
 // uhc_batch_kernels.hip -- the batch's small kernels beside the step kernels: set_state, the sticky tiers' list kernel, the gate.
 #include "uhc_physics_impl.h"
+#include "uhc_internal.h"
 
 // set_state: scatter rows of (qpos, qvel) into the listed envs, clear warm start / flags
 __global__ void uhc_set_state_kernel(DevState s, int nq, int nv, int nu, const int* env_ids, int n, const double* qpos,

@@ -11,7 +11,10 @@
 #include <string>
 #include <vector>
 
+#include "uhc_api_check.h"  // uhc_internal_set_error (defined below), HIP_OK
+#include "uhc_env_plan.h"   // UhcBatchInfo
 #include "uhc_host.h"
+#include "uhc_internal.h"
 #include "uhc_launch.h"
 #include "uhc_plan.h"
 
@@ -39,11 +42,6 @@ static hipError_t uhc_set_lds_limit(size_t lds_bytes, size_t lds_bytes_fast, siz
     }
     return hipSuccess;
 }
-extern "C" hipError_t uhc_launch_tier_lists(const int* tier, const int* d_active, int n_env, int* tier_now, int* lists, int* counts, int* cursors, int* fin,
-                                            const int* cost, const int* fresh, int* order, int launch4, int* pend3, hipStream_t stream);
-extern "C" hipError_t uhc_launch_gate(const int* started, int want, int* waited, long long* trace, hipStream_t stream);
-extern "C" hipError_t uhc_launch_set_state(const DevState* s, int nq, int nv, int nu, const int* env_ids, int n,
-                                           const double* qpos, const double* qvel, int* mask, hipStream_t stream);
 
 static thread_local std::string g_err;
 static int fail(const char* fmt, ...) {
@@ -55,12 +53,6 @@ static int fail(const char* fmt, ...) {
     g_err = buf;
     return 1;
 }
-#define HIP_OK(expr)                                                                      \
-    do {                                                                                  \
-        hipError_t e__ = (expr);                                                          \
-        if (e__ != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(e__));      \
-    } while (0)
-
 extern "C" const char* uhc_last_error(void) { return g_err.c_str(); }
 extern "C" int32_t uhc_abi_version(void) { return UHC_ABI_VERSION; }
 // what kind of build this library is: bit 0 = the solver's measurement switches are compiled in (-DUHC_EXPERIMENTS: UHC_DEBUG_EXP_* act), bit 1 = stage
@@ -255,7 +247,6 @@ static int alloc_state(UhcBatch* b, const UhcModel* const* models, const int32_t
     return 0;
 }
 
-extern "C" void uhc_batch_free(UhcBatch* b);
 // knobs and plan first (every refusal that does not need the device), then the device: from its first allocation the batch is owned by a
 // handle that frees it, so no exit leaks device memory
 extern "C" int32_t uhc_batch_create(const UhcModel* const* models, int32_t n_models, const int32_t* h_env_model, int32_t n_env,
@@ -605,8 +596,7 @@ extern "C" int32_t uhc_batch_simulate(UhcBatch* b, const double* d_action, const
     return launch(b, 0, d_action, d_target_base, d_active);
 }
 
-extern "C" hipError_t uhc_launch_set_state_masked(const DevState* s, int nq, int nv, int nu, int n_env, const int* select, const double* qpos,
-                                                  const double* qvel, int* mask, hipStream_t stream);
+// ------------------------------------------------------------------ what the env layer (uhc_env_capi.cpp) reads and asks of a batch: uhc_internal.h
 // env layer: set_state + forward on the envs flagged in d_select (rows of d_qpos / d_qvel are indexed by env)
 extern "C" int uhc_internal_set_state_masked(UhcBatch* b, const int* d_select, const double* d_qpos, const double* d_qvel) {
     HIP_OK(hipSetDevice(b->device));
@@ -618,17 +608,17 @@ extern "C" int uhc_internal_set_state_masked(UhcBatch* b, const int* d_select, c
     return 0;
 }
 
-extern "C" int uhc_internal_trailing_free(UhcBatch* b) { return b->n_trailing_free; }
 extern "C" int* uhc_internal_env_model(UhcBatch* b, int* n_models) { *n_models = b->n_models; return const_cast<int*>(b->A.s.env_model); }
-// ------------------------------------------------------------------ internal accessors for the env layer (uhc_env_capi.cpp)
 extern "C" int uhc_internal_set_error(const char* msg) { return fail("%s", msg); }
-extern "C" int uhc_internal_batch_info(UhcBatch* b, int* n_env, int* nq, int* nv, int* nu, int* nbody, int* action_dim, int* vf_dim,
-                                       double* dt, double* base_rot_inv, void** stream, int** reset_mask) {
-    *n_env = b->n_env; *nq = b->A.t.nq; *nv = b->A.t.nv; *nu = b->A.t.nu; *nbody = b->A.t.nbody;
-    *action_dim = b->A.c.action_dim; *vf_dim = b->A.c.rfc_mode == 1 ? 6 : b->A.c.rfc_mode == 2 ? b->A.c.n_vf_body * b->A.c.body_vf_dim : 0;
-    *dt = b->A.t.timestep * b->A.c.n_substeps;
-    for (int k = 0; k < 4; k++) base_rot_inv[k] = b->A.c.base_rot_inv[k];
-    *stream = (void*)b->stream;
-    *reset_mask = b->reset_mask;
-    return 0;
+extern "C" hipStream_t uhc_internal_stream(UhcBatch* b) { return b->stream; }
+extern "C" int* uhc_internal_reset_mask(UhcBatch* b) { return b->reset_mask; }
+extern "C" UhcBatchInfo uhc_internal_batch_info(UhcBatch* b) {
+    const KernelArgs& A = b->A;
+    UhcBatchInfo I = {};
+    I.n_env = b->n_env; I.nq = A.t.nq; I.nv = A.t.nv; I.nu = A.t.nu; I.nbody = A.t.nbody;
+    I.action_dim = A.c.action_dim; I.vf_dim = A.c.rfc_mode == 1 ? 6 : A.c.rfc_mode == 2 ? A.c.n_vf_body * A.c.body_vf_dim : 0;
+    I.dt = A.t.timestep * A.c.n_substeps;
+    for (int k = 0; k < 4; k++) I.base_rot_inv[k] = A.c.base_rot_inv[k];
+    I.n_trailing_free = b->n_trailing_free;
+    return I;
 }

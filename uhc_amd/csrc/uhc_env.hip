@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "uhc_device_env.h"
+#include "uhc_internal.h"
 
 #define LANE ((int)threadIdx.x)
 #define WAVE 64

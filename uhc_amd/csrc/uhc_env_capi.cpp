@@ -1,34 +1,16 @@
 // uhc_env_capi.cpp -- host side of the env layer C-ABI (include/uhc_amd.h, "Env layer").
 #include <hip/hip_runtime.h>
 
-#include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/uhc_amd.h"
 #include "uhc_api_check.h"  // uhc_internal_set_error, HIP_OK
 #include "uhc_device_env.h"
-#include "uhc_expert_math.h"  // XfTree: the kinematic tree uhc_env_live_push hands its kernel
-
-extern "C" hipError_t uhc_launch_live_push(const EnvArgs* E, const XfTree* tree, double dt, int cap, int n_models, double* bank, double* prev_qpos,
-                                           int* live_len, int* dropped, int* live_base, int* live_moved, int slide, const double* body_pos,
-                                           const double* body_ipos, const int* env_ids, int n, const double* qpos, const double* root_record,
-                                           const int* restart, const int* model, hipStream_t s);
-extern "C" hipError_t uhc_launch_env_pre(const EnvArgs* E, const int* d_active, hipStream_t s);
-extern "C" hipError_t uhc_launch_env_post(int mode, const EnvArgs* E, const double* d_action, const int* d_active, hipStream_t s);
-extern "C" hipError_t uhc_launch_env_reset_stage(const EnvArgs* E, const int* env_ids, int n, const double* noise, double* out_qpos,
-                                                 double* out_qvel, hipStream_t s);
-extern "C" hipError_t uhc_launch_env_set_next(const EnvArgs* E, const int* env_ids, int n, const int* clip_ids, const int* fr_start,
-                                              const int* fr_len, const double* noise, hipStream_t s);
-extern "C" hipError_t uhc_launch_env_auto_stage(const EnvArgs* E, double* out_qpos, double* out_qvel, int* select, hipStream_t s);
-extern "C" int* uhc_internal_env_model(UhcBatch* b, int* n_models);
-extern "C" int uhc_internal_set_state_masked(UhcBatch* b, const int* d_select, const double* d_qpos, const double* d_qvel);
-extern "C" hipError_t uhc_launch_env_assign(const EnvArgs* E, const int* env_ids, int n, const int* clip_ids, const int* fr_start,
-                                            const int* fr_len, hipStream_t s);
-// accessors implemented in uhc_capi.cpp
-extern "C" int uhc_internal_batch_info(UhcBatch* b, int* n_env, int* nq, int* nv, int* nu, int* nbody, int* action_dim, int* vf_dim,
-                                       double* dt, double* base_rot_inv, void** stream, int** reset_mask);
-extern "C" int uhc_internal_trailing_free(UhcBatch* b);
+#include "uhc_env_plan.h"     // plan_env: what an env is, decided without the device
+#include "uhc_expert_math.h"  // XfTree, LiveState: what uhc_env_live_push hands its kernel
+#include "uhc_internal.h"     // the launchers of uhc_env.hip / uhc_live.hip, the batch's accessors
 
 struct UhcEnv {
     UhcBatch* b = nullptr;
@@ -38,83 +20,47 @@ struct UhcEnv {
     int* select = nullptr;
     int n_clips = 0;
     int64_t n_frames = 0;
-    // live targets (uhc_env_live_*): the env's own bank, one stream of `live_cap` frames per env; the memory stays until uhc_env_free
-    bool live = false;
-    int live_cap = 0, live_alloc_cap = 0, live_models = 0;
-    double live_dt = 0.0;
-    XfTree live_tree = {};
-    double *live_bank = nullptr, *live_prev_qpos = nullptr, *live_beta = nullptr, *live_body_pos = nullptr, *live_body_ipos = nullptr;
-    int *live_len = nullptr, *live_dropped = nullptr, *live_clip_start = nullptr;
-    // sliding (uhc_env_live_slide): frames slid off / records copied since the restart, per env; live_begin switches it off
-    bool live_slide = false;
-    int *live_base = nullptr, *live_moved = nullptr;
+    LiveState live;  // live targets (uhc_env_live_*)
 };
 #define NOT_WHILE_LIVE(e, who) \
-    if ((e)->live) return uhc_internal_set_error(who ": the env is in live mode (uhc_env_live_begin): a stream has no window to assign or queue -- push a restart row and uhc_env_reset, or uhc_env_live_end first")
+    if ((e)->live.on) return uhc_internal_set_error(who ": the env is in live mode (uhc_env_live_begin): a stream has no window to assign or queue -- push a restart row and uhc_env_reset, or uhc_env_live_end first")
 
 template <class T>
 static int dalloc(UhcEnv* e, size_t n, T** p) {
     void* q = nullptr;
     if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) return uhc_internal_set_error("uhc_env: hipMalloc failed");
-    hipMemset(q, 0, (n ? n : 1) * sizeof(T));
     e->allocs.push_back(q);
+    HIP_OK(hipMemset(q, 0, (n ? n : 1) * sizeof(T)));
     *p = (T*)q;
     return 0;
 }
+static hipStream_t stream_of(UhcEnv* e) { return uhc_internal_stream(e->b); }  // (per call: uhc_batch_set_stream may have changed it)
 
+// the plan first (every refusal; none needs the device), then the device: from its creation the env is owned by a handle that frees it, so no exit leaks
 extern "C" int32_t uhc_env_create(UhcBatch* b, const UhcEnvDesc* d, UhcEnv** out) {
     if (!b || !d || !out) return uhc_internal_set_error("uhc_env_create: null argument");
-    if (d->obs_v < 0 || d->obs_v > 6) return uhc_internal_set_error("uhc_env_create: obs_v must be 0 .. 6");
-    if (d->obs_v == 3 && (d->fut_frames < 1 || d->fut_frames > 64 || d->fut_skip < 0)) return uhc_internal_set_error("uhc_env_create: obs_v 3 needs 1 <= fut_frames <= 64, skip >= 0");
-    if (d->term_body != 0 && d->term_body != 1) return uhc_internal_set_error("uhc_env_create: term_body must be 0 (cfg.env_term_body 'body') or 1 ('root')");
-    if (d->reward_v < 0 || d->reward_v > 5) return uhc_internal_set_error("uhc_env_create: reward_v must be 0 .. 5 (implicit, explicit, implicit_v1_mul, explicit_mul, implicit_v2, implicit_v3)");
-    UhcEnv* e = new UhcEnv();
+    EnvArgs plan;
+    const std::string refused = plan_env(uhc_internal_batch_info(b), *d, &plan);
+    if (!refused.empty()) return uhc_internal_set_error(refused.c_str());
+
+    std::unique_ptr<UhcEnv, void (*)(UhcEnv*)> owner(new UhcEnv(), uhc_env_free);
+    UhcEnv* e = owner.get();
     e->b = b;
+    e->E = plan;
     EnvArgs& E = e->E;
-    memset(&E, 0, sizeof E);
-    void* stream;
-    int* mask;
-    uhc_internal_batch_info(b, &E.n_env, &E.nq, &E.nv, &E.nu, &E.nbody, &E.action_dim, &E.vf_dim, &E.dt, E.base_rot_inv, &stream, &mask);
-    // free objects (expert["obj_pose"], humanoid_im.py:1284-1287): the LAST num_obj bodies of the model, one free joint each; what is in front of
-    // them is the humanoid -- the reference's qpos_lim / qvel_lim / body_lim (humanoid_im.py:113-115), which its observations, rewards and
-    // termination stop at
-    E.n_obj = d->num_obj;
-    if (E.n_obj < 0 || E.n_obj > uhc_internal_trailing_free(b)) { delete e; return uhc_internal_set_error("uhc_env_create: num_obj exceeds the free bodies at the end of the model"); }
-    E.nqh = E.nq - 7 * E.n_obj; E.nvh = E.nv - 6 * E.n_obj; E.nbh = E.nbody - E.n_obj;
-    const int nb = E.nbh - 1;
-    // ball-joint humanoid (robot.ball): free root + one ball joint per further body
-    E.ball = E.nqh == 7 + 4 * (nb - 1) && E.nvh == 6 + 3 * (nb - 1) && nb > 1 && E.nqh != E.nvh + 1;
-    if ((E.nqh != E.nvh + 1 && !E.ball) || E.nq > 192 || nb < 1 || nb > 64) { delete e; return uhc_internal_set_error("uhc_env_create: hinge humanoid (free root + scalar joints) or ball-joint humanoid (free root + one ball joint per body), followed by num_obj free bodies, nq <= 192, expected"); }
-    if (E.ball && (d->obs_v != 2 || d->reward_v != 0)) { delete e; return uhc_internal_set_error("uhc_env_create: the ball-joint env has observation v2 (get_full_obs_v2_quat) and reward 0 (world_rfc_implicit_quat)"); }
-    E.has_shape = d->has_shape;
-    E.obs_v = d->obs_v;
-    E.reward_v = d->reward_v;
-    E.obs_flags = d->obs_flags;
-    E.term_body = d->term_body;
-    if (d->obs_v == 0)  // [heading] qpos[2:] velocities expert joint angles [phase]; get_full_obs never appends the shape
-        E.obs_dim = (d->obs_flags & 1) + (E.nqh - 2) + ((d->obs_flags & 8) ? 6 : E.nvh) + E.nu + ((d->obs_flags >> 2) & 1);
-    else
-        E.obs_dim = (d->obs_v == 6 ? 8 + E.nvh + 2 * nb + 11 * (nb - 1) : (d->obs_v == 5 ? 300 : 304) + (d->obs_v == 1 ? 20 : 14) * nb) + (d->has_shape ? 17 : 0);
-    if (d->obs_v == 4) E.obs_dim = 28 + 26 * (nb - 1) + (d->has_shape ? 17 : 0);  // get_full_obs_v4 (:769-861): global block | shape | one row of 26 per non-root body
-    if (E.ball) E.obs_dim = 7 + 4 * nb + (E.nu + 6) + 3 + 6 * nb + 8 * nb + (d->has_shape ? 17 : 0);  // get_full_obs_v2_quat (:668-756)
-    if (d->obs_v == 0) E.has_shape = 0;
-    E.fut_frames = d->obs_v == 3 ? d->fut_frames : 1;
-    E.fut_skip = d->obs_v == 3 ? d->fut_skip : 0;
-    E.obs_dim *= E.fut_frames;
-    E.env_episode_len = d->env_episode_len;
-    E.expert_trail_steps = d->env_expert_trail_steps;
-    for (int k = 0; k < 5; k++) E.ee_body[k] = d->ee_body[k];
-    E.body_diff_thresh = d->body_diff_thresh;
-    for (int k = 0; k < 16; k++) E.rw[k] = d->reward_weights[k];
+    const size_t N = E.n_env, nb = E.nbh - 1;
     double *w, *rjw;
-    if (dalloc(e, nb, &w) || dalloc(e, nb, &rjw)) { delete e; return 1; }
+    if (dalloc(e, nb, &w) || dalloc(e, nb, &rjw)) return 1;
+    const std::vector<double> ones(nb, 1.0);
     HIP_OK(hipMemcpy(w, d->jpos_diffw, nb * sizeof(double), hipMemcpyHostToDevice));
-    E.jpos_diffw = w;
-    {
-        std::vector<double> ones(nb, 1.0);
-        HIP_OK(hipMemcpy(rjw, d->reward_jpos_diffw ? d->reward_jpos_diffw : ones.data(), nb * sizeof(double), hipMemcpyHostToDevice));
-        E.rjw = rjw;
-    }
+    HIP_OK(hipMemcpy(rjw, d->reward_jpos_diffw ? d->reward_jpos_diffw : ones.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+    E.jpos_diffw = w, E.rjw = rjw;
+    if (dalloc(e, N, &E.clip_id) || dalloc(e, N, &E.e_start) || dalloc(e, N, &E.e_len) || dalloc(e, N, &E.cur_t) || dalloc(e, N, &E.start_ind) ||
+        dalloc(e, N * E.nu, &E.target_base) || dalloc(e, N * E.nq, &E.qpos_prev) || dalloc(e, N * E.obs_dim, &E.obs) || dalloc(e, N, &E.reward) ||
+        dalloc(e, N * 6, &E.reward_parts) || dalloc(e, N, &E.height_lb) || dalloc(e, N, &E.percent) || dalloc(e, N, &E.body_diff) || dalloc(e, N, &E.done) || dalloc(e, N, &E.fail) ||
+        dalloc(e, N, &E.end) || dalloc(e, N * E.nq, &e->stage_qpos) || dalloc(e, N * E.nv, &e->stage_qvel) || dalloc(e, N, &e->select) ||
+        dalloc(e, N, &E.next_clip) || dalloc(e, N, &E.next_start) || dalloc(e, N, &E.next_len) || dalloc(e, N, &E.has_next) || dalloc(e, N, &E.consumed) ||
+        dalloc(e, N * E.nu, &E.next_noise) || dalloc(e, 2 * N, &E.episode) || dalloc(e, 5 * N, &E.snapshot)) return 1;
     void* p; int64_t cnt;
     uhc_batch_field(b, UHC_F_QPOS, &p, &cnt); E.qpos = (const double*)p;
     uhc_batch_field(b, UHC_F_QVEL, &p, &cnt); E.qvel = (const double*)p;
@@ -122,14 +68,7 @@ extern "C" int32_t uhc_env_create(UhcBatch* b, const UhcEnvDesc* d, UhcEnv** out
     uhc_batch_field(b, UHC_F_XQUAT, &p, &cnt); E.xquat = (const double*)p;
     uhc_batch_field(b, UHC_F_XIPOS, &p, &cnt); E.xipos = (const double*)p;
     uhc_batch_field(b, UHC_F_FAIL, &p, &cnt); E.sim_fail = (const int*)p;
-    const size_t N = E.n_env;
-    if (dalloc(e, N, &E.clip_id) || dalloc(e, N, &E.e_start) || dalloc(e, N, &E.e_len) || dalloc(e, N, &E.cur_t) || dalloc(e, N, &E.start_ind) ||
-        dalloc(e, N * E.nu, &E.target_base) || dalloc(e, N * E.nq, &E.qpos_prev) || dalloc(e, N * E.obs_dim, &E.obs) || dalloc(e, N, &E.reward) ||
-        dalloc(e, N * 6, &E.reward_parts) || dalloc(e, N, &E.height_lb) || dalloc(e, N, &E.percent) || dalloc(e, N, &E.body_diff) || dalloc(e, N, &E.done) || dalloc(e, N, &E.fail) ||
-        dalloc(e, N, &E.end) || dalloc(e, N * E.nq, &e->stage_qpos) || dalloc(e, N * E.nv, &e->stage_qvel) || dalloc(e, N, &e->select) ||
-        dalloc(e, N, &E.next_clip) || dalloc(e, N, &E.next_start) || dalloc(e, N, &E.next_len) || dalloc(e, N, &E.has_next) || dalloc(e, N, &E.consumed) ||
-        dalloc(e, N * E.nu, &E.next_noise) || dalloc(e, 2 * N, &E.episode) || dalloc(e, 5 * N, &E.snapshot)) { delete e; return 1; }
-    *out = e;
+    *out = owner.release();
     return 0;
 }
 extern "C" void uhc_env_free(UhcEnv* e) {
@@ -170,7 +109,7 @@ extern "C" int32_t uhc_env_field(UhcEnv* e, int32_t f, void** p, int64_t* n) {
 extern "C" int32_t uhc_env_set_bank(UhcEnv* e, const double* d_frames, int64_t n_frames, const int32_t* d_clip_start,
                                     const double* d_clip_beta, int32_t n_clips) {
     if (!e || !d_frames || !d_clip_start || !d_clip_beta || n_frames < 1 || n_clips < 1) return uhc_internal_set_error("uhc_env_set_bank: bad argument");
-    e->live = false;  // (a caller's bank ends live mode, like uhc_env_live_end)
+    e->live.on = false;  // (a caller's bank ends live mode, like uhc_env_live_end)
     e->E.bank = d_frames; e->E.clip_start = d_clip_start; e->E.clip_beta = d_clip_beta;
     e->n_clips = n_clips; e->n_frames = n_frames;
     e->E.obj_pose = nullptr;  // rows of another bank
@@ -194,11 +133,6 @@ extern "C" int32_t uhc_env_set_clip_models(UhcEnv* e, const int32_t* d_clip_mode
     e->E.env_model = em;
     return 0;
 }
-static hipStream_t stream_of(UhcEnv* e) {
-    void* s; int* m; int a; double d; double br[4];
-    uhc_internal_batch_info(e->b, &a, &a, &a, &a, &a, &a, &a, &d, br, &s, &m);
-    return (hipStream_t)s;
-}
 extern "C" int32_t uhc_env_assign(UhcEnv* e, const int32_t* ids, int32_t n, const int32_t* clip_ids, const int32_t* fr_start, const int32_t* fr_len) {
     if (!e || !ids || !clip_ids || !fr_start || !fr_len || n < 1) return uhc_internal_set_error("uhc_env_assign: bad argument");
     NOT_WHILE_LIVE(e, "uhc_env_assign");
@@ -213,9 +147,7 @@ extern "C" int32_t uhc_env_reset(UhcEnv* e, const int32_t* ids, int32_t n, const
     hipStream_t s = stream_of(e);
     HIP_OK(uhc_launch_env_reset_stage(&e->E, ids, n, d_noise, e->stage_qpos, e->stage_qvel, s));
     if (uhc_batch_set_state(e->b, ids, n, e->stage_qpos, e->stage_qvel)) return 1;  // set_state + forward on those envs
-    void* st; int* mask; int a; double d; double br[4];
-    uhc_internal_batch_info(e->b, &a, &a, &a, &a, &a, &a, &a, &d, br, &st, &mask);
-    HIP_OK(uhc_launch_env_post(1, &e->E, nullptr, mask, s));  // observation of the reset envs (mask = envs just reset)
+    HIP_OK(uhc_launch_env_post(1, &e->E, nullptr, uhc_internal_reset_mask(e->b), s));  // observation of the reset envs (mask = envs just reset)
     return 0;
 }
 extern "C" int32_t uhc_env_set_next(UhcEnv* e, const int32_t* ids, int32_t n, const int32_t* clip_ids, const int32_t* fr_start, const int32_t* fr_len,
@@ -281,44 +213,44 @@ extern "C" int32_t uhc_env_live_begin(UhcEnv* e, int32_t cap, int32_t n_body, co
     const size_t N = e->E.n_env;
     if ((long long)N * cap > 0x7fffffffLL) return uhc_internal_set_error("uhc_env_live_begin: n_env x cap is beyond 2^31 - 1 frames");
     HIP_OK(hipStreamSynchronize(stream_of(e)));  // (a step in flight may still read the bank the tables below are about to clear)
-    if (cap > e->live_alloc_cap) {
-        if (e->live) (void)uhc_env_live_end(e);  // (the bank about to be freed may be the installed one: no bank until this call succeeds)
-        if (e->live_bank) (void)hipFree(take_alloc(e, e->live_bank));
-        e->live_bank = nullptr, e->live_alloc_cap = 0;
+    if (cap > e->live.alloc_cap) {
+        if (e->live.on) (void)uhc_env_live_end(e);  // (the bank about to be freed may be the installed one: no bank until this call succeeds)
+        if (e->live.bank) (void)hipFree(take_alloc(e, e->live.bank));
+        e->live.bank = nullptr, e->live.alloc_cap = 0;
         void* q = nullptr;
         if (hipMalloc(&q, N * cap * UHC_FRAME_STRIDE * sizeof(double)) != hipSuccess) {
             (void)hipGetLastError();
             return uhc_internal_set_error(("uhc_env_live_begin: cap = " + std::to_string(cap) + ": no memory for n_env x cap x 4672 bytes").c_str());
         }
         e->allocs.push_back(q);
-        e->live_bank = (double*)q, e->live_alloc_cap = cap;
+        e->live.bank = (double*)q, e->live.alloc_cap = cap;
     }
-    if (!e->live_len && (dalloc(e, N * XF_NQ, &e->live_prev_qpos) || dalloc(e, N, &e->live_len) || dalloc(e, N, &e->live_dropped) ||
-                         dalloc(e, N, &e->live_clip_start) || dalloc(e, N * 17, &e->live_beta) || dalloc(e, N, &e->live_base) || dalloc(e, N, &e->live_moved) ||
-                         dalloc(e, (size_t)n_models * XF_NBODY * 3, &e->live_body_pos) || dalloc(e, (size_t)n_models * XF_NBODY * 3, &e->live_body_ipos)))
+    if (!e->live.len && (dalloc(e, N * XF_NQ, &e->live.prev_qpos) || dalloc(e, N, &e->live.len) || dalloc(e, N, &e->live.dropped) ||
+                         dalloc(e, N, &e->live.clip_start) || dalloc(e, N * 17, &e->live.beta) || dalloc(e, N, &e->live.base) || dalloc(e, N, &e->live.moved) ||
+                         dalloc(e, (size_t)n_models * XF_NBODY * 3, &e->live.body_pos) || dalloc(e, (size_t)n_models * XF_NBODY * 3, &e->live.body_ipos)))
         return 1;
     hipStream_t s = stream_of(e);
-    HIP_OK(hipMemsetAsync(e->live_len, 0, N * sizeof(int), s));  // every stream is cleared: an append without a restart is dropped
-    HIP_OK(hipMemsetAsync(e->live_dropped, 0, N * sizeof(int), s));
-    HIP_OK(hipMemsetAsync(e->live_base, 0, N * sizeof(int), s));
-    HIP_OK(hipMemsetAsync(e->live_moved, 0, N * sizeof(int), s));
-    HIP_OK(hipMemsetAsync(e->live_prev_qpos, 0, N * XF_NQ * sizeof(double), s));
+    HIP_OK(hipMemsetAsync(e->live.len, 0, N * sizeof(int), s));  // every stream is cleared: an append without a restart is dropped
+    HIP_OK(hipMemsetAsync(e->live.dropped, 0, N * sizeof(int), s));
+    HIP_OK(hipMemsetAsync(e->live.base, 0, N * sizeof(int), s));
+    HIP_OK(hipMemsetAsync(e->live.moved, 0, N * sizeof(int), s));
+    HIP_OK(hipMemsetAsync(e->live.prev_qpos, 0, N * XF_NQ * sizeof(double), s));
     // every slot is zeroed and every env points at a window of ONE frame inside its own stream: a reset or a step before the first push reads zeros,
     // never a frame outside the bank (the env kernels clamp to e_len - 1, and e_start of an earlier bank means nothing here)
-    HIP_OK(hipMemsetAsync(e->live_bank, 0, N * cap * UHC_FRAME_STRIDE * sizeof(double), s));
+    HIP_OK(hipMemsetAsync(e->live.bank, 0, N * cap * UHC_FRAME_STRIDE * sizeof(double), s));
     std::vector<int> cs(N), ones(N, 1), iota(N);
     for (size_t i = 0; i < N; i++) cs[i] = (int)(i * cap), iota[i] = (int)i;
-    HIP_OK(hipMemcpy(e->live_clip_start, cs.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(e->live.clip_start, cs.data(), N * sizeof(int), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(e->E.e_start, cs.data(), N * sizeof(int), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(e->E.e_len, ones.data(), N * sizeof(int), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(e->E.clip_id, iota.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    if (d_beta) HIP_OK(hipMemcpy(e->live_beta, d_beta, N * 17 * sizeof(double), hipMemcpyDeviceToDevice));
-    else HIP_OK(hipMemset(e->live_beta, 0, N * 17 * sizeof(double)));
-    HIP_OK(hipMemcpy(e->live_body_pos, d_body_pos, (size_t)n_models * XF_NBODY * 3 * sizeof(double), hipMemcpyDeviceToDevice));
-    HIP_OK(hipMemcpy(e->live_body_ipos, d_body_ipos, (size_t)n_models * XF_NBODY * 3 * sizeof(double), hipMemcpyDeviceToDevice));
+    if (d_beta) HIP_OK(hipMemcpy(e->live.beta, d_beta, N * 17 * sizeof(double), hipMemcpyDeviceToDevice));
+    else HIP_OK(hipMemset(e->live.beta, 0, N * 17 * sizeof(double)));
+    HIP_OK(hipMemcpy(e->live.body_pos, d_body_pos, (size_t)n_models * XF_NBODY * 3 * sizeof(double), hipMemcpyDeviceToDevice));
+    HIP_OK(hipMemcpy(e->live.body_ipos, d_body_ipos, (size_t)n_models * XF_NBODY * 3 * sizeof(double), hipMemcpyDeviceToDevice));
     HIP_OK(hipStreamSynchronize(s));
-    e->live = true, e->live_slide = false, e->live_cap = cap, e->live_models = n_models, e->live_dt = dt, e->live_tree = tree;
-    e->E.bank = e->live_bank, e->E.clip_start = e->live_clip_start, e->E.clip_beta = e->live_beta;
+    e->live.on = true, e->live.slide = false, e->live.cap = cap, e->live.models = n_models, e->live.dt = dt, e->live.tree = tree;
+    e->E.bank = e->live.bank, e->E.clip_start = e->live.clip_start, e->E.clip_beta = e->live.beta;
     e->E.obj_pose = nullptr, e->E.clip_model = nullptr, e->E.env_model = em;
     e->n_clips = (int)N, e->n_frames = (int64_t)N * cap;
     return 0;
@@ -330,40 +262,38 @@ extern "C" int32_t uhc_env_live_push(UhcEnv* e, const int32_t* d_env_ids, int32_
     if (n < 0) return uhc_internal_set_error("uhc_env_live_push: n < 0");
     if (n == 0) return 0;  // (nothing to push: no launch, and nothing of the env is read)
     if (!e) return uhc_internal_set_error("uhc_env_live_push: the env e is NULL");
-    if (!e->live) return uhc_internal_set_error("uhc_env_live_push: the env is not in live mode (uhc_env_live_begin)");
-    HIP_OK(uhc_launch_live_push(&e->E, &e->live_tree, e->live_dt, e->live_cap, e->live_models, e->live_bank, e->live_prev_qpos, e->live_len, e->live_dropped,
-                                e->live_base, e->live_moved, e->live_slide ? 1 : 0, e->live_body_pos, e->live_body_ipos, d_env_ids, n, d_qpos, d_root_quat_record,
-                                d_restart, d_model, stream_of(e)));
+    if (!e->live.on) return uhc_internal_set_error("uhc_env_live_push: the env is not in live mode (uhc_env_live_begin)");
+    HIP_OK(uhc_launch_live_push(&e->E, &e->live, d_env_ids, n, d_qpos, d_root_quat_record, d_restart, d_model, stream_of(e)));
     return 0;
 }
 extern "C" int32_t uhc_env_live_slide(UhcEnv* e, int32_t on) {
     if (!e) return uhc_internal_set_error("uhc_env_live_slide: the env e is NULL");
-    if (!e->live) return uhc_internal_set_error("uhc_env_live_slide: the env is not in live mode (uhc_env_live_begin)");
+    if (!e->live.on) return uhc_internal_set_error("uhc_env_live_slide: the env is not in live mode (uhc_env_live_begin)");
     if (on && e->E.obs_v == 0 && (e->E.obs_flags & 4))
         return uhc_internal_set_error("uhc_env_live_slide: the env's observation carries the phase word (obs_v 0 with obs_flags & 4): cur_t / len would jump at a slide");
-    e->live_slide = on != 0;
+    e->live.slide = on != 0;
     return 0;
 }
 extern "C" int32_t uhc_env_live_window(UhcEnv* e, int32_t** d_base, int32_t** d_moved) {
     if (!e) return uhc_internal_set_error("uhc_env_live_window: the env e is NULL");
-    if (!e->live) return uhc_internal_set_error("uhc_env_live_window: the env is not in live mode (uhc_env_live_begin)");
-    if (d_base) *d_base = e->live_base;
-    if (d_moved) *d_moved = e->live_moved;
+    if (!e->live.on) return uhc_internal_set_error("uhc_env_live_window: the env is not in live mode (uhc_env_live_begin)");
+    if (d_base) *d_base = e->live.base;
+    if (d_moved) *d_moved = e->live.moved;
     return 0;
 }
 extern "C" int32_t uhc_env_live_view(UhcEnv* e, double** d_frames, int32_t** d_len, int32_t** d_dropped, int32_t* cap) {
     if (!e) return uhc_internal_set_error("uhc_env_live_view: the env e is NULL");
-    if (!e->live) return uhc_internal_set_error("uhc_env_live_view: the env is not in live mode (uhc_env_live_begin)");
-    if (d_frames) *d_frames = e->live_bank;
-    if (d_len) *d_len = e->live_len;
-    if (d_dropped) *d_dropped = e->live_dropped;
-    if (cap) *cap = e->live_cap;
+    if (!e->live.on) return uhc_internal_set_error("uhc_env_live_view: the env is not in live mode (uhc_env_live_begin)");
+    if (d_frames) *d_frames = e->live.bank;
+    if (d_len) *d_len = e->live.len;
+    if (d_dropped) *d_dropped = e->live.dropped;
+    if (cap) *cap = e->live.cap;
     return 0;
 }
 extern "C" int32_t uhc_env_live_end(UhcEnv* e) {
     if (!e) return uhc_internal_set_error("uhc_env_live_end: the env e is NULL");
-    if (!e->live) return uhc_internal_set_error("uhc_env_live_end: the env is not in live mode (uhc_env_live_begin)");
-    e->live = false;
+    if (!e->live.on) return uhc_internal_set_error("uhc_env_live_end: the env is not in live mode (uhc_env_live_begin)");
+    e->live.on = false;
     e->E.bank = nullptr, e->E.clip_start = nullptr, e->E.clip_beta = nullptr, e->E.clip_model = nullptr;
     e->n_clips = 0, e->n_frames = 0;
     return 0;

@@ -30,6 +30,19 @@ struct XfTree {
     int max_depth;
 };
 
+// HOST: the live state of an env (uhc_env_live_*): its own bank, one stream of `cap` frames per env.  Owned by the UhcEnv (uhc_env_capi.cpp), whose
+// memory stays until uhc_env_free; read by uhc_live.hip's launcher, which packs it into its kernels' arguments.
+struct LiveState {
+    bool on = false;     // the env is in live mode (uhc_env_live_begin .. uhc_env_live_end / uhc_env_set_bank)
+    bool slide = false;  // uhc_env_live_slide; live_begin switches it off
+    int cap = 0, alloc_cap = 0, models = 0;
+    double dt = 0.0;
+    XfTree tree = {};
+    double *bank = nullptr, *prev_qpos = nullptr, *beta = nullptr, *body_pos = nullptr, *body_ipos = nullptr;
+    int *len = nullptr, *dropped = nullptr, *clip_start = nullptr;
+    int *base = nullptr, *moved = nullptr;  // frames slid off / records copied since the restart, per env
+};
+
 // HOST: h_parent [24] (the root's parent is -1 and every other parent precedes its child), h_ee_body [5] (0 .. 23) -> T; "" or what is wrong, `who` in front
 static inline std::string xf_tree_fill(const char* who, const int32_t* h_parent, const int32_t* h_ee_body, XfTree* T) {
     *T = XfTree{};

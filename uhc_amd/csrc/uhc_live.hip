@@ -21,6 +21,7 @@
 #include "../../include/uhc_amd.h"
 #include "uhc_device_env.h"
 #include "uhc_expert_math.h"
+#include "uhc_internal.h"
 #include "uhc_live_window.h"
 #include "uhc_seq.h"
 
@@ -156,22 +157,20 @@ __global__ void __launch_bounds__(64 * LV_WAVES) uhc_live_slide_kernel(const int
     }
 }
 
-// E's per-env arrays and the live state -> one launch on s (two with slide != 0: the slide of the listed envs, then the append); n >= 1
-extern "C" hipError_t uhc_launch_live_push(const EnvArgs* E, const XfTree* tree, double dt, int cap, int n_models, double* bank, double* prev_qpos,
-                                           int* live_len, int* dropped, int* live_base, int* live_moved, int slide, const double* body_pos,
-                                           const double* body_ipos, const int* env_ids, int n, const double* qpos, const double* root_record,
+// E's per-env arrays and the live state -> one launch on s (two while sliding: the slide of the listed envs, then the append); n >= 1
+extern "C" hipError_t uhc_launch_live_push(const EnvArgs* E, const LiveState* L, const int* env_ids, int n, const double* qpos, const double* root_record,
                                            const int* restart, const int* model, hipStream_t s) {
-    if (slide) {
-        hipLaunchKernelGGL(uhc_live_slide_kernel, dim3((unsigned)(((long long)n + LV_WAVES - 1) / LV_WAVES)), dim3(64 * LV_WAVES), 0, s, env_ids, restart, n, bank,
-                           live_len, live_base, live_moved, E->e_len, E->start_ind, E->cur_t, E->n_env, cap);
+    if (L->slide) {
+        hipLaunchKernelGGL(uhc_live_slide_kernel, dim3((unsigned)(((long long)n + LV_WAVES - 1) / LV_WAVES)), dim3(64 * LV_WAVES), 0, s, env_ids, restart, n, L->bank,
+                           L->len, L->base, L->moved, E->e_len, E->start_ind, E->cur_t, E->n_env, L->cap);
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }
     LiveArgs A = {};
     A.env_ids = env_ids, A.qpos = qpos, A.root_record = root_record, A.restart = restart, A.model = model, A.n = n;
-    A.bank = bank, A.prev_qpos = prev_qpos, A.live_len = live_len, A.dropped = dropped, A.live_base = live_base, A.live_moved = live_moved;
-    A.body_pos = body_pos, A.body_ipos = body_ipos;
-    A.n_env = E->n_env, A.cap = cap, A.n_models = n_models, A.dt = dt, A.tree = *tree;
+    A.bank = L->bank, A.prev_qpos = L->prev_qpos, A.live_len = L->len, A.dropped = L->dropped, A.live_base = L->base, A.live_moved = L->moved;
+    A.body_pos = L->body_pos, A.body_ipos = L->body_ipos;
+    A.n_env = E->n_env, A.cap = L->cap, A.n_models = L->models, A.dt = L->dt, A.tree = L->tree;
     A.e_len = E->e_len, A.e_start = E->e_start, A.clip_id = E->clip_id, A.env_model = E->env_model, A.height_lb = E->height_lb;
     hipLaunchKernelGGL(uhc_live_push_kernel, dim3((unsigned)(((long long)n + 2 * LV_WAVES - 1) / (2 * LV_WAVES))), dim3(64 * LV_WAVES), 0, s, A);
     return hipGetLastError();
