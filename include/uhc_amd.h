@@ -29,7 +29,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define UHC_ABI_VERSION 11  /* 11: uhc_expert_frames (the clip bank's frame records computed on the device) -- uhc_eval_record / uhc_eval_metrics came later and are purely additive: still 11, as are uhc_surface_* / uhc_eval_record_pose; 10: uhc_build_flags; 9: UHC_F_REDO bits 29 / 30 (tier 4), swept-substep bits 8 .. 28; uhc_rollout_record counts int64 [7] */
+#define UHC_ABI_VERSION 11  /* 11: uhc_expert_frames (the clip bank's frame records computed on the device) -- uhc_eval_record / uhc_eval_metrics came later and are purely additive: still 11, as are uhc_surface_* / uhc_eval_record_pose and uhc_policy_*; 10: uhc_build_flags; 9: UHC_F_REDO bits 29 / 30 (tier 4), swept-substep bits 8 .. 28; uhc_rollout_record counts int64 [7] */
 
 /* joint / geom type codes (MuJoCo numbering) */
 enum { UHC_JNT_FREE = 0, UHC_JNT_BALL = 1, UHC_JNT_SLIDE = 2, UHC_JNT_HINGE = 3 };
@@ -693,6 +693,52 @@ int32_t uhc_smpl_mesh(void* stream, UhcSmplMesh* mesh, int32_t n_seq, const int6
                       const int32_t* d_seq_model, const double* d_betas, const double* d_pose_aa, int64_t pose_stride, const double* d_trans,
                       int64_t trans_stride, int64_t n_rows_total, double floor_z, double* d_vert, double* d_joints, double* d_row_out,
                       double* d_seq_means, double* d_row_zmin, int32_t* d_bad, int32_t* h_bad);
+
+/* ------------------------------------------------------------------ a frozen policy: raw observations -> action means, without the framework
+ * The mean action of PolicyGaussian (uhc/khrylib/rl/core/policy_gaussian.py:9-31) and PolicyMCP (uhc/models/policy_mcp.py:9-37) behind the observation
+ * filter ZFilter(update = False) (uhc/khrylib/utils/zfilter.py:55-64), float64, products on v_mfma_f64_16x16x4_f64.  Same conventions as the functions above:
+ * `stream` is a hipStream_t (NULL = the default stream), every argument is checked before the first HIP call, every sum has a fixed order and no atomics (two
+ * runs are bit-identical; a row's action is bit-identical whatever the batch size and wherever the row sits in the batch), no value in any array can send a
+ * read or a write outside the arrays.  (Purely additive: UHC_ABI_VERSION stays 11.)
+ *
+ * A policy is a list of nets, each a chain of layers y = act(x W^T + b) on the filtered observation.  UHC_POLICY_GAUSSIAN: one net, the trunk and its linear
+ * head (last width act_dim).  UHC_POLICY_MCP: n_nets - 1 primitive nets of equal shape (last width act_dim), then the composer (last width n_nets - 1, its
+ * last layer activated like the others), mean = sum_p softmax(composer)_p mean_p.
+ *
+ * uhc_policy_create: h_n_layers int32 [n_nets]; h_widths / h_acts int32, the nets' layers one after the other (sum of h_n_layers entries): each layer's
+ *   output width and its activation (UHC_ACT_*; UHC_ACT_GELU is the exact erf form); h_w / h_b: per layer, in the same order, HOST arrays in nn.Linear layout
+ *   ([out][in], [out]).  The weights are copied to the current device and repacked there once.  Refused by name: a non-positive dimension, an unknown
+ *   activation, primitives of unequal shape, a composer whose last width is not the number of primitives, a non-finite weight.  max_rows: the largest n_rows
+ *   of a uhc_policy_act; the handle owns what a call keeps between its kernels (nothing is allocated in a call), so it serves one stream at a time.
+ * uhc_policy_set_filter: the frozen statistics of the filter from the HOST: n, h_mean [obs_dim], h_S [obs_dim] (RunningStat's sum of squared deviations:
+ *   std = sqrt(S / (n - 1)), |mean| while n <= 1), demean, destd, clip (0 = none): y = clip((x - mean) / (std + 1e-8), +-clip), the arithmetic of
+ *   uhc_filter_apply -- the filtered observation has the same bits.  h_mean = h_S = NULL, or no call at all: observations go in as they are.  Waits for the device.
+ * uhc_policy_set_params: new weights for the same shapes, per layer as in uhc_policy_create; on_device != 0: DEVICE arrays (the live parameters of a policy
+ *   that is still being trained), else HOST arrays (checked for non-finite entries; device arrays are not read by the host).  Copied and repacked on `stream`.
+ *   Host arrays are the caller's again when the call returns (it waits for `stream`); device arrays must stay valid and unchanged until the work enqueued on
+ *   `stream` has run -- the call does not wait for it.
+ * uhc_policy_act: d_obs: row r at d_obs + r * obs_stride (in doubles, >= obs_dim: a view into a wider array is read where it lies); d_state_out
+ *   [n_rows][obs_dim] or NULL: the filtered observation; d_mean [n_rows][act_dim]; d_weight_out [n_rows][n_primitives] or NULL (MCP only): the composer's
+ *   weights.  One launch per layer (all nets at once) plus one for the MCP sum, a straight chain on `stream`: it may be captured in a HIP graph.
+ *   n_rows == 0 succeeds and launches nothing; n_rows > max_rows and obs_stride < obs_dim are refused.
+ * uhc_policy_save / uhc_policy_load: a flat little-endian file: the 8 bytes "UHCPOLCY", int32 version (1), kind, obs_dim, act_dim, n_nets, n_layers [n_nets],
+ *   widths, acts; int32 has_filter, demean, destd, 0; double clip, n, mean [obs_dim], S [obs_dim]; then per net and layer W [out][in] and b [out] as doubles.
+ *   The round trip is bit-exact.  save waits for the device.  uhc_policy_dims: what a loaded handle holds (any pointer may be NULL); packed_bytes: the size of
+ *   the repacked weights and biases a call reads. */
+enum { UHC_POLICY_GAUSSIAN = 0, UHC_POLICY_MCP = 1 };
+enum { UHC_ACT_NONE = 0, UHC_ACT_TANH = 1, UHC_ACT_RELU = 2, UHC_ACT_SIGMOID = 3, UHC_ACT_GELU = 4 };
+typedef struct UhcPolicy UhcPolicy;
+int32_t uhc_policy_create(int32_t kind, int32_t obs_dim, int32_t act_dim, int32_t max_rows, int32_t n_nets, const int32_t* h_n_layers,
+                          const int32_t* h_widths, const int32_t* h_acts, const double* const* h_w, const double* const* h_b, UhcPolicy** out);
+void uhc_policy_free(UhcPolicy* policy);
+int32_t uhc_policy_dims(const UhcPolicy* policy, int32_t* kind, int32_t* obs_dim, int32_t* act_dim, int32_t* max_rows, int32_t* n_primitives,
+                        int64_t* packed_bytes);
+int32_t uhc_policy_set_filter(UhcPolicy* policy, double n, const double* h_mean, const double* h_S, int32_t demean, int32_t destd, double clip);
+int32_t uhc_policy_set_params(void* stream, UhcPolicy* policy, const double* const* w, const double* const* b, int32_t on_device);
+int32_t uhc_policy_act(void* stream, UhcPolicy* policy, int32_t n_rows, const double* d_obs, int64_t obs_stride, double* d_state_out, double* d_mean,
+                       double* d_weight_out);
+int32_t uhc_policy_save(const UhcPolicy* policy, const char* path);
+int32_t uhc_policy_load(const char* path, int32_t max_rows, UhcPolicy** out);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

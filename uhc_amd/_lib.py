@@ -26,6 +26,8 @@ SYMBOLS = [
     "uhc_qpos_smpl", "uhc_smpl6d_qpos",
     "uhc_env_live_slide", "uhc_env_live_window",
     "uhc_smpl_mesh_create", "uhc_smpl_mesh_free", "uhc_smpl_mesh",
+    "uhc_policy_create", "uhc_policy_free", "uhc_policy_dims", "uhc_policy_set_filter", "uhc_policy_set_params", "uhc_policy_act",
+    "uhc_policy_save", "uhc_policy_load",
 ]
 
 
@@ -128,6 +130,19 @@ def lib():
         L.uhc_smpl_mesh_free.restype = None
         L.uhc_smpl_mesh.argtypes = [P, P, I, P, P, I, P, P, P, C.c_int64, P, C.c_int64, C.c_int64, D, P, P, P, P, P, P, C.POINTER(I)]
         L.uhc_smpl_mesh_create.restype = L.uhc_smpl_mesh.restype = I
+    if hasattr(L, "uhc_policy_act"):  # (additive within ABI 11)
+        PI, PP = C.POINTER(I), C.POINTER(P)
+        L.uhc_policy_create.argtypes = [I, I, I, I, I, PI, PI, PI, PP, PP, PP]
+        L.uhc_policy_free.argtypes = [P]
+        L.uhc_policy_free.restype = None
+        L.uhc_policy_dims.argtypes = [P, PI, PI, PI, PI, PI, C.POINTER(C.c_int64)]
+        L.uhc_policy_set_filter.argtypes = [P, D, P, P, I, I, D]
+        L.uhc_policy_set_params.argtypes = [P, P, PP, PP, I]
+        L.uhc_policy_act.argtypes = [P, P, I, P, C.c_int64, P, P, P]
+        L.uhc_policy_save.argtypes = [P, C.c_char_p]
+        L.uhc_policy_load.argtypes = [C.c_char_p, I, PP]
+        for f in ("create", "dims", "set_filter", "set_params", "act", "save", "load"):
+            getattr(L, "uhc_policy_" + f).restype = I
     _lib = L
     return L
 

@@ -577,6 +577,30 @@ def _eval_seqs(self, take_keys, loader):
     return out
 
 
+def _device_policy(self, max_rows):
+    """cfg.policy_build == "device": the agent's policy and filter AS THEY ARE NOW in the library's frozen policy (uhc_amd.policy_ops.DevicePolicy) -- one
+    handle per batch size, made on first use; later calls copy the live weights (uhc_policy_set_params) and the filter's statistics into it again."""
+    from ..policy_ops import DevicePolicy
+    cache = self.__dict__.setdefault("_device_policies", {})
+    dp = cache.get(int(max_rows))
+    if dp is None or dp._modules is not self.policy_net:
+        dp = cache[int(max_rows)] = DevicePolicy.from_modules(self.policy_net, self.running_state, max_rows=int(max_rows), device=self.env.device)
+    else:
+        dp.refresh()
+        dp.set_filter(self.running_state)
+    return dp
+
+
+def _export_policy(self, path):
+    """The current policy (mean action) and the filter's frozen statistics as the flat file uhc_policy_load reads: what a C program deploys behind
+    include/uhc_amd.h (INTEGRATION: the deployment recipe)."""
+    from ..policy_ops import DevicePolicy
+    dp = DevicePolicy.from_modules(self.policy_net, self.running_state, max_rows=1, device=self.env.device)
+    dp.save(path)
+    dp.close()
+    return path
+
+
 def _eval_seqs_device(self, ev, take_keys, loader, n):
     """eval_seqs with cfg.eval_build == "device": the same chunks, assign / reset, filter calls and simulation calls as the host loop above, but the
     trajectory is appended on the device (uhc_eval_record) and scored there (uhc_eval_metrics).  The step loop reads nothing back when cfg.fail_safe is
@@ -642,12 +666,20 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
         xquat_f = ev.sim.field(S.F_XQUAT) if surf else None
         t = 0
 
+        # cfg.policy_build "device": the library's frozen policy reads ev.obs where it lies (filter fused, the statistics as the reset's push above left
+        # them: what update=False normalises with from here on) and writes one fixed action tensor; rows of envs that are not active are computed and ignored
+        dpol = _device_policy(self, n) if getattr(cfg, "policy_build", "torch") == "device" else None
+        action_buf = torch.zeros((n, dpol.act_dim), dtype=torch.float64, device=dev) if dpol is not None else None
+
         def step():
             nonlocal state
             if surf:
                 EO.record_pose(rec, 0, xpos_f, xquat_f, active)
             EO.record(rec, 0, t, qpos_f, xpos_f, clip0, lens_d, active)
-            action = self.policy_net.select_action(self.trans_policy(state), True).to(torch.float64).contiguous()
+            if dpol is not None:
+                action = dpol.mean(ev.obs, out=action_buf)
+            else:
+                action = self.policy_net.select_action(self.trans_policy(state), True).to(torch.float64).contiguous()
             ev.step(action, active)
             if surf:
                 EO.record_pose(rec, 1, xpos_f, xquat_f, active, done=ev.done)
@@ -661,7 +693,8 @@ def _eval_seqs_device(self, ev, take_keys, loader, n):
                         qp = torch.cat([qp, qpos_f[ti, ql:]], 1)
                         qv = torch.cat([qv, ev.sim.field(S.F_QVEL)[ti, ev.qvel_lim:]], 1)
                     ev.sim.set_state(qp.contiguous(), qv.contiguous(), ti.to(torch.int32))
-            state = self.running_state(ev.obs.to(self.dtype), update=False) if self.running_state is not None else ev.obs.to(self.dtype)
+            if dpol is None:
+                state = self.running_state(ev.obs.to(self.dtype), update=False) if self.running_state is not None else ev.obs.to(self.dtype)
 
         while True:
             for _ in range(block):
@@ -769,7 +802,10 @@ def _track_stream(self, source, n_steps, n_env=None, head=3, cap=None):
         ev.live_begin(int(n_steps) + int(head) + 1)
     else:
         ev.live_begin(int(cap), slide=True)
-    tracker = StreamTracker(ev, self.policy_net, self.running_state, dtype=self.dtype)
+    if getattr(cfg, "policy_build", "torch") == "device":  # the library's frozen policy: one uhc_policy_act per step, filter fused
+        tracker = StreamTracker(ev, _device_policy(self, n), None, dtype=self.dtype, policy="device")
+    else:
+        tracker = StreamTracker(ev, self.policy_net, self.running_state, dtype=self.dtype)
     tracker.begin(torch.stack([torch.as_tensor(source(t)).to(ev.device, torch.float64) for t in range(head)], 1))
     out = torch.zeros((n, int(n_steps), int(ev.model.nq)), dtype=torch.float64, device=ev.device)
     ended = torch.full((n,), int(n_steps), dtype=torch.int64, device=ev.device)
@@ -782,6 +818,7 @@ def _track_stream(self, source, n_steps, n_env=None, head=3, cap=None):
 
 
 AgentCopycat.track_stream = _track_stream
+AgentCopycat.export_policy = _export_policy
 AgentCopycat.eval_policy = _eval_policy
 AgentCopycat.eval_seqs = _eval_seqs
 AgentCopycat.eval_seq = _eval_seq

@@ -129,6 +129,12 @@ class Config(Base_Config):
             raise ValueError(f"eval_mesh: false or the directory of the SMPL model files, got {self.eval_mesh!r}")
         if self.eval_mesh and self.eval_surface:
             raise ValueError("eval_mesh and eval_surface write the same result keys (pentration, skate, float, contact): set one of them")
+        # who computes the mean action in the device evaluation loop (eval_build "device") and in track_stream: "torch" -- ZFilter(update=False), the
+        # framework's forward pass, .contiguous() --, "device" -- the library's frozen policy (uhc_policy_act: filter fused, one launch per layer), the
+        # weights and the filter's statistics copied into it at the start of every chunk / session.  The training sampler always stays with the framework
+        self.policy_build = g("policy_build", "torch")
+        if self.policy_build not in ("torch", "device"):
+            raise ValueError(f"policy_build: 'torch' or 'device', got {self.policy_build!r}")
         self.ppo_dtype = g("ppo_dtype", "float64")
         # data-parallel gradient exchange: the dtype on the wire.  float32 (default): SURVEY 8e's 32 MB per optimisation epoch; the local
         # gradient means travel scaled by the rank's sample count and are divided by the global count in the parameters' own float64, so the
